@@ -210,6 +210,26 @@ def _pmc_traffic(args, kname):
         "in-run rocprofv3 --pmc: (2*FETCH %.0f + WRITE %.0f) KiB" % (vals["FETCH_SIZE"], vals["WRITE_SIZE"]))
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _dump_outputs(path, arrays):
+    """Writes every name -> tensor of `arrays` to path/<name>.npy as float32.  A tensor past its share of DUMP_MAX_BYTES is
+    written as <name>_sample.npy: its flattened entries at sorted indices drawn from a fixed seed, so two runs of the same
+    arguments sample the same entries."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_MAX_BYTES // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.numel(), cap))
+            a, name = a.reshape(-1)[torch.from_numpy(idx).to(a.device)], name + "_sample"
+        a = a.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        print("bench: wrote %s (%s float32)" % (os.path.join(path, name + ".npy"), "x".join(map(str, a.shape))), file=sys.stderr)
+
+
 def _self_launch(n):
     """Re-run this command as an n-rank torch.distributed.run job on this node (127.0.0.1, a free port)."""
     import socket
@@ -257,7 +277,12 @@ def main():
                     help="timed steps of the training step's single-pass f16 throughput mode (prec='f16'; reported beside "
                          "train_ms_per_step with its gradient deviation, never instead of it; 0 = skip)")
     ap.add_argument("--infer-only", action="store_true", help="the headline loop alone (A/B scripts): every secondary leg off")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last of them returned (rank 0's "
+                    "sdf_pred, batch x n_qry) to DIR/sdf_pred.npy in float32, to compare two builds output for output; past "
+                    "64 MB a fixed seeded sample of it")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.infer_only:
         for k in ("cpu_sample", "f16_steps", "f32_steps", "noise_steps", "c4_steps", "mesh_steps", "ldm_steps", "train_steps",
                   "gt_train_steps", "train_f16_steps", "pmc"):
@@ -320,6 +345,8 @@ def main():
     dt = time.perf_counter() - t0
     if args.pmc_child:      # counter pass under rocprofv3: only the timed loop's launches are wanted
         return
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, {"sdf_pred": out})
     rank_ms = [dt / args.steps * 1e3]
     if dist is not None:
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)

@@ -125,6 +125,21 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert r["ms_per_step_rank_min_max"][0] <= r["ms_per_step_rank_min_max"][1]
 
 
+def test_bench_dump_outputs_is_the_same_for_the_same_arguments(tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's sdf_pred (batch x n_qry, float32) lands in DIR/sdf_pred.npy with the
+    JSON line still the only line on stdout; the inputs are seeded, so runs with other step counts write the same array."""
+    import json
+    import numpy as np
+    common = ["--gpus", "1", "--warmup", "1", "--batch", "2", "--n-qry", "4096", "--img-size", "64", "--infer-only"]
+    for d, steps in (("a", "2"), ("b", "3")):
+        out = run([os.path.join(ROOT, "bench.py"), "--steps", steps, "--dump-outputs", str(tmp_path / d)] + common, ROOT)
+        lines = [ln for ln in out.splitlines() if ln.strip()]
+        assert len(lines) == 1 and json.loads(lines[0])["steps"] == int(steps), lines
+    a, b = np.load(tmp_path / "a" / "sdf_pred.npy"), np.load(tmp_path / "b" / "sdf_pred.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 4096) and np.isfinite(a).all() and a.std() > 0
+    assert np.array_equal(a, b)
+
+
 def test_bench_self_launches_two_ranks_on_one_gpu():
     """`python bench.py --gpus 2` WITHOUT torch.distributed.run: bench.py spawns its two ranks itself (the form the
     driver's single-GPU command has).  S3D_BENCH_BACKEND=gloo lets both ranks share the one GPU of the test box — every

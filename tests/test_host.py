@@ -127,6 +127,26 @@ def test_bench_self_launch_builds_a_torchrun_job(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs_writes_float32_within_the_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: an output within the cap is written whole, in its shape, as float32; past the cap a sample of
+    the cap's size is written, the same entries in every run."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    t = torch.randn(4, 1000, dtype=torch.float64)
+    bench._dump_outputs(str(tmp_path / "whole"), {"sdf_pred": t})
+    a = np.load(tmp_path / "whole" / "sdf_pred.npy")
+    assert a.dtype == np.float32 and a.shape == (4, 1000) and np.array_equal(a, t.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 1000)
+    for d in ("s1", "s2"):
+        bench._dump_outputs(str(tmp_path / d), {"sdf_pred": t})
+    s1, s2 = np.load(tmp_path / "s1" / "sdf_pred_sample.npy"), np.load(tmp_path / "s2" / "sdf_pred_sample.npy")
+    assert s1.dtype == np.float32 and s1.nbytes == 4 * 1000 and np.array_equal(s1, s2)
+    assert np.isin(s1, t.float().numpy()).all()
+
+
 def test_generator3d_refuses_the_reference_dead_post_processing_branches():
     """reconstruct.py:205-240: with_normals / refinement_step / simplify_nfaces run through model.decode(p, c).logits under
     autograd w.r.t. the points — dead in the reference (its model has no decode()).  They must not be accepted and ignored."""
