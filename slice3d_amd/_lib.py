@@ -15,6 +15,7 @@ PREC_F32 = 0
 PREC_F16X3 = 1
 PREC_F16 = 2          # single-pass f16 MFMA: throughput mode, not fp32-class (inference only)
 PREC_BF16 = 3         # the decoder's attention / FFN GEMMs on the bf16 MFMA, the rest as PREC_F16 (Slices3DRegModel inference only)
+PREC = {"f32": PREC_F32, "f16x3": PREC_F16X3, "f16": PREC_F16, "bf16": PREC_BF16}
 PROF_UNET, PROF_LATENT, PROF_SAMPLE, PROF_ATTN, PROF_FFN, PROF_FFN_FINAL, PROF_VGG, PROF_SAMPLE_PYR = range(8)
 PROF_NAMES = ("unet_encode", "latent_build", "sample_tokens", "attn_layer", "ffn_layer", "ffn_final", "vgg_loss",
               "sample_pyramid")
@@ -230,6 +231,19 @@ def check(rc, what):
     if rc != 0:
         msg = load().s3d_last_error()
         raise S3dError("%s failed (rc=%d): %s" % (what, rc, msg.decode() if msg else "?"))
+
+
+def prec_code(name, allowed):
+    """PREC_* value of a precision name; KeyError(name) outside the caller's `allowed` names."""
+    if name not in allowed:
+        raise KeyError(name)
+    return PREC[name]
+
+
+def stream_ptr(device):
+    """torch's current stream on `device` as the hipStream_t argument of the C ABI."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def ptr(t):

@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .models import HipModel
 
 
 def _gn(ch):
@@ -57,7 +58,11 @@ class AttentionBlock(nn.Module):
         self.proj_out = nn.Conv1d(channels, channels, 1)
 
 
-class UNetModel(nn.Module):
+class UNetModel(HipModel, nn.Module):
+    _NO_LIB = ("UNetModel(backend=%r) cannot compute: the HIP library is required; there is no CPU fallback in the "
+               "product path")
+    _NOT_EVAL = "UNetModel computes the eval-mode forward; call model.eval()"
+
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions,
                  dropout=0, channel_mult=(1, 2, 4, 8), num_heads=-1, use_scale_shift_norm=False, resblock_updown=False,
                  backend="hip", prec="f16x3", fuse_gn=True, branch_streams=False, defer_finish=False):
@@ -129,20 +134,11 @@ class UNetModel(nn.Module):
         self._ws = None
 
     # ------------------------------------------------------------------------------------------
-    def _require_lib(self):
-        if self._lib is None:
-            raise _lib.S3dError("UNetModel(backend=%r) cannot compute: the HIP library is required; there is no CPU "
-                                "fallback in the product path" % self.backend)
-        return self._lib
-
-    def _dev(self):
+    def _device(self):
         return self.time_embed[0].weight.device
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self._dev()).cuda_stream)
-
     def _precv(self):
-        return {"f16x3": _lib.PREC_F16X3, "f16": _lib.PREC_F16, "f32": _lib.PREC_F32}[self.prec]
+        return _lib.prec_code(self.prec, ("f16x3", "f16", "f32"))
 
     def _attn_precv(self):
         # prec='f16' (single-pass convolutions, the throughput mode): the attention operators keep their split-precision form
@@ -172,7 +168,7 @@ class UNetModel(nn.Module):
 
     def repack(self):
         self._require_lib()
-        if self._dev().type != "cuda":
+        if self._device().type != "cuda":
             raise _lib.S3dError("move the model to the GPU (model.cuda())")
         self._packed = {}
         for mod in self.modules():
@@ -395,7 +391,7 @@ class UNetModel(nn.Module):
     def _add_nchw(self, a, b):
         """h + c_fmap (openaimodel.py:735-746) with the feature map read in the reference's NCHW layout: one launch."""
         self._finish_pending()
-        b = b.to(device=self._dev(), dtype=torch.float32).contiguous()
+        b = b.to(device=self._device(), dtype=torch.float32).contiguous()
         n, c, h, w = b.shape
         if tuple(a.shape) != (n, h, w, c):
             return self._add(a, self._to_nhwc(b))
@@ -405,7 +401,7 @@ class UNetModel(nn.Module):
 
     def _to_nhwc(self, x, cpad=None):
         lib = self._lib
-        x = x.to(device=self._dev(), dtype=torch.float32).contiguous()
+        x = x.to(device=self._device(), dtype=torch.float32).contiguous()
         n, c, h, w = x.shape
         cpad = cpad or c
         out = torch.empty((n, h, w, cpad), dtype=torch.float32, device=x.device)
@@ -497,13 +493,11 @@ class UNetModel(nn.Module):
         """openaimodel.py:710-757: x (N, in_channels, H, W), timesteps (N,), c_fmaps {'f1'..'f5'} NCHW feature maps
         added after input blocks 0, 4, 7, 10, 12 -> (N, out_channels, H, W)."""
         lib = self._require_lib()
-        if self.training:
-            raise RuntimeError("UNetModel computes the eval-mode forward; call model.eval()")
+        self._require_eval()
         if context is not None or y is not None:
             raise NotImplementedError("cross-attention context / class labels are not built")
-        if self._packed_key is None or self._packed_key != self._params_key():
-            self.repack()
-        dev = self._dev()
+        self._ensure_packed()
+        dev = self._device()
         n = x.shape[0]
         self._pending = None
         t = timesteps.to(device=dev, dtype=torch.float32).contiguous()

@@ -123,7 +123,7 @@ class DeviceMISE:
         self._idx = torch.empty(max((resolution_0 + 1) ** 3, 1 << 16), dtype=torch.int32, device=self.device)
 
     def _stream(self):
-        return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+        return self._L.stream_ptr(self.device)
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -186,7 +186,7 @@ def marching_cubes_device(volume, isovalue, pad_value=None):
     pv = 0.0 if pad_value is None else float(pad_value)
     nb = lib.s3d_mc_dev_workspace_bytes(nx, ny, nz, pad)
     ws = torch.empty(nb, dtype=torch.uint8, device=vol.device)
-    st = C.c_void_p(torch.cuda.current_stream(vol.device).cuda_stream)
+    st = _lib.stream_ptr(vol.device)
     nv, nt = C.c_long(0), C.c_long(0)
     args = (vol.data_ptr(), is64, nx, ny, nz, pad, pv, float(isovalue), ws.data_ptr(), nb)
     _lib.check(lib.s3d_mc_dev_count(*args, C.byref(nv), C.byref(nt), st), "s3d_mc_dev_count")

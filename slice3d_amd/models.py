@@ -136,6 +136,134 @@ class VGGPerceptualLoss(nn.Module):
         self.weights = [1.0 / 2.6, 1.0 / 4.8, 1.0 / 3.7, 1.0 / 5.6, 1.0 * 10 / 1.5]
 
 
+# ------------------------------------------------------------------------------------------
+# C-ABI parameter structs (include/slice3d_hip.h) from the module tree, for the eval-mode packs and the training step alike.
+# `pick(tensor)` is the pointer a slot gets: `data_ptr` for the values, a trainer's gradient slot for the gradients (None
+# for a tensor without one).  The builders touch neither the library nor the device.
+# ------------------------------------------------------------------------------------------
+BN_ALL = (0, 1, 2, 3)          # S3dConvParams.bn slots: weight, bias, running_mean, running_var
+data_ptr = torch.Tensor.data_ptr      # the `pick` of the values
+
+
+def conv_params(conv, pick, bn=None, bn_slots=BN_ALL):
+    cp = _lib.S3dConvParams()
+    cp.w = pick(conv.weight)
+    cp.b = pick(conv.bias) if conv.bias is not None else None
+    if bn is not None:
+        bn_tensors = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        for i in bn_slots:
+            cp.bn[i] = pick(bn_tensors[i])
+    return cp
+
+
+def vgg16_convs(module, slices):
+    """(conv, the BatchNorm after it) of the 13 convolutions of a vgg16_bn.features tree sliced as `slices`."""
+    return [(getattr(getattr(module, _slice_of(idx, slices)), str(idx)),
+             getattr(getattr(module, _slice_of(idx + 1, slices)), str(idx + 1))) for idx, _, _ in _VGG16_CFG]
+
+
+def unet_params(model, pick, last_bn=BN_ALL):
+    """S3dUNetParams of model.slices_generator.  last_bn: the bn slots conv5_3 (enc[12]) gets from down5_.41, the
+    BatchNorm of the reference's x5_, which nothing reads."""
+    g = model.slices_generator
+    up = _lib.S3dUNetParams()
+    for i, (conv, bn) in enumerate(vgg16_convs(g, _VGG16_SLICES)):
+        up.enc[i] = conv_params(conv, pick, bn, BN_ALL if i < 12 else last_bn)
+    up.trans_c = conv_params(g.trans_c, pick)
+    for i in range(4):
+        u = getattr(g, "up%d" % (i + 1))
+        dc = u.conv.double_conv
+        up.trans_up[i] = conv_params(getattr(g, "trans_up%d" % (i + 1)), pick)
+        up.up_t[i] = conv_params(u.up, pick)
+        up.up_c1[i] = conv_params(getattr(dc, "0"), pick, getattr(dc, "1"))
+        up.up_c2[i] = conv_params(getattr(dc, "3"), pick, getattr(dc, "4"))
+    up.outc = conv_params(g.outc.conv, pick)
+    up.emds = pick(g.emds.weight)
+    up.n_slices = model.n_slices
+    return up
+
+
+def fill_layers(hp, model, pick):
+    """The att_decoder layers and fc_out of a head struct (S3dHeadParams or S3dGtHeadParams)."""
+    for i, layer in enumerate(model.att_decoder.layers):
+        lp = hp.layer[i]
+        lp.in_proj_w, lp.in_proj_b = pick(layer.self_attn.in_proj_weight), pick(layer.self_attn.in_proj_bias)
+        lp.out_proj_w, lp.out_proj_b = pick(layer.self_attn.out_proj.weight), pick(layer.self_attn.out_proj.bias)
+        lp.lin1_w, lp.lin1_b = pick(layer.linear1.weight), pick(layer.linear1.bias)
+        lp.lin2_w, lp.lin2_b = pick(layer.linear2.weight), pick(layer.linear2.bias)
+        lp.norm1_w, lp.norm1_b = pick(layer.norm1.weight), pick(layer.norm1.bias)
+        lp.norm2_w, lp.norm2_b = pick(layer.norm2.weight), pick(layer.norm2.bias)
+    hp.fc_out_w, hp.fc_out_b = pick(model.fc_out[0].weight), pick(model.fc_out[0].bias)
+
+
+def head_params(model, pick):
+    hp = _lib.S3dHeadParams()
+    hp.fc_p_w, hp.fc_p_b = pick(model.fc_p.weight), pick(model.fc_p.bias)
+    hp.fc_s_w, hp.fc_s_b = pick(model.fc_s.weight), pick(model.fc_s.bias)
+    fill_layers(hp, model, pick)
+    return hp
+
+
+def vgg_params(model, pick):
+    """S3dVggParams of the perceptual loss' frozen VGG19; the struct holds the (3,) mean / std it points to."""
+    loss = model.vggptlossfunc
+    vp = _lib.S3dVggParams()
+    for i, (idx, _, _) in enumerate(_VGG19_CONVS):
+        vp.conv[i] = conv_params(getattr(getattr(loss.vgg, _slice_of(idx, _VGG19_SLICES)), str(idx)), pick)
+    vp.keep = (loss.mean.reshape(3).contiguous(), loss.std.reshape(3).contiguous())
+    vp.mean, vp.std = pick(vp.keep[0]), pick(vp.keep[1])
+    return vp
+
+
+class HipModel:
+    """Engine plumbing of the models that compute through libslice3d_hip.so.  A model supplies `_device()`, `backend`,
+    `_lib` (None without the library), the `_ws` dict and the texts `_NO_LIB` (% backend) and `_NOT_EVAL`.  UNetModel
+    uses the library / eval / stream / repack-on-change parts, with a `_params_key` of its own."""
+
+    def _require_lib(self):
+        if self._lib is None:
+            raise _lib.S3dError(self._NO_LIB % self.backend)
+        return self._lib
+
+    def _require_eval(self):
+        if self.training:
+            raise RuntimeError(self._NOT_EVAL)
+
+    def _stream(self):
+        return _lib.stream_ptr(self._device())
+
+    def _workspace(self, key, nbytes):
+        buf = self._ws.get(key)
+        if buf is None or buf.numel() < nbytes or buf.device != self._device():
+            buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self._device())
+            self._ws[key] = buf
+        return buf
+
+    def _f32(self, t):
+        return t.to(device=self._device(), dtype=torch.float32).contiguous()
+
+    def _params_key(self):
+        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
+
+    def _ensure_packed(self):
+        if self._packed_key is None or self._packed_key != self._params_key():
+            self.repack()
+
+    def _check_packable(self):
+        for t in list(self.parameters()) + list(self.buffers()):
+            if t.is_floating_point() and (t.dtype != torch.float32 or not t.is_contiguous()):
+                raise _lib.S3dError("parameters must be contiguous fp32")
+        dev = self._device()
+        if dev.type != "cuda":
+            raise _lib.S3dError("model parameters are on %s; move the model to the GPU (model.cuda())" % dev)
+
+    def _pack(self, symbol, params, nbytes):
+        """A new packed weight image: the library's `symbol` (s3d_*_pack) applied to the parameter struct."""
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=self._device())
+        _lib.check(getattr(self._lib, symbol)(C.byref(params), buf.data_ptr(), nbytes, self._stream()), symbol)
+        return buf
+
+
 class LatentCode:
     """Result of encode(): the per-object state every query decode needs (the 'c' of ConvONet's
     encode/decode split).  All tensors are fp32 on the model's device, channels-last."""
@@ -187,7 +315,13 @@ class _TrainForward(torch.autograd.Function):
         return (None, None) + tuple(grads)
 
 
-class Slices3DRegModel(nn.Module):
+class Slices3DRegModel(HipModel, nn.Module):
+    _NO_LIB = ("Slices3DRegModel(backend=%r) cannot compute: the HIP library is required (backend='hip'); there is no "
+               "CPU fallback in the product path")
+    _NOT_EVAL = ("encode / decode compute the eval-mode forward (running-stat BatchNorm, no dropout): call model.eval() "
+                 "for inference.  In train mode use model(batch) (autograd) or "
+                 "slice3d_amd.trainer.HipTrainer.train_step (the fused step)")
+
     def __init__(self, img_size=128, n_slices=12, mode="train", backend="hip", prec="f32"):
         super().__init__()
         self.mode = mode
@@ -201,7 +335,7 @@ class Slices3DRegModel(nn.Module):
         self.vggptlossfunc = VGGPerceptualLoss()
         self.n_slices = n_slices
         self.backend = backend
-        self.prec = {"f32": _lib.PREC_F32, "f16x3": _lib.PREC_F16X3, "f16": _lib.PREC_F16, "bf16": _lib.PREC_BF16}[prec]
+        self.prec = _lib.PREC[prec]
         self.prec_name = prec
         self.train_dropout = 0.1     # nn.TransformerEncoderLayer's default, what the reference trains with (models.py:18)
         self.train_seed = 0
@@ -218,19 +352,6 @@ class Slices3DRegModel(nn.Module):
     # ------------------------------------------------------------------------------------------
     # engine plumbing
     # ------------------------------------------------------------------------------------------
-    def _require_lib(self):
-        if self._lib is None:
-            raise _lib.S3dError("Slices3DRegModel(backend=%r) cannot compute: the HIP library is required "
-                                "(backend='hip'); there is no CPU fallback in the product path" % self.backend)
-        return self._lib
-
-    def _require_eval(self):
-        if self.training:
-            raise RuntimeError(
-                "encode / decode compute the eval-mode forward (running-stat BatchNorm, no dropout): call "
-                "model.eval() for inference.  In train mode use model(batch) (autograd) or "
-                "slice3d_amd.trainer.HipTrainer.train_step (the fused step)")
-
     def _train_engine(self):
         """The HIP training engine behind train-mode model(batch): its own flat gradient buffer (param.grad is left
         to autograd), dropout = self.train_dropout, dropout streams from self.train_seed."""
@@ -258,94 +379,15 @@ class Slices3DRegModel(nn.Module):
     def _device(self):
         return self.fc_p.weight.device
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self._device()).cuda_stream)
-
-    def _workspace(self, key, nbytes):
-        buf = self._ws.get(key)
-        if buf is None or buf.numel() < nbytes or buf.device != self._device():
-            buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self._device())
-            self._ws[key] = buf
-        return buf
-
-    def _params_key(self):
-        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
-
-    def _conv_params(self, conv, bn=None):
-        cp = _lib.S3dConvParams()
-        cp.w = conv.weight.data_ptr()
-        cp.b = conv.bias.data_ptr() if conv.bias is not None else None
-        if bn is not None:
-            for i, t in enumerate((bn.weight, bn.bias, bn.running_mean, bn.running_var)):
-                cp.bn[i] = t.data_ptr()
-        return cp
-
     def repack(self):
         """(Re)build the MFMA-fragment-ordered, BN-folded weight images from the current parameters."""
         lib = self._require_lib()
-        for t in list(self.parameters()) + list(self.buffers()):
-            if t.is_floating_point() and (t.dtype != torch.float32 or not t.is_contiguous()):
-                raise _lib.S3dError("parameters must be contiguous fp32")
-        dev = self._device()
-        if dev.type != "cuda":
-            raise _lib.S3dError("model parameters are on %s; move the model to the GPU (model.cuda())" % dev)
-        g = self.slices_generator
-        up = _lib.S3dUNetParams()
-        seqs = {name: getattr(g, name) for name, _, _ in _VGG16_SLICES}
-        for i, (idx, _, _) in enumerate(_VGG16_CFG):
-            conv = getattr(seqs[_slice_of(idx, _VGG16_SLICES)], str(idx))
-            bn = getattr(seqs[_slice_of(idx + 1, _VGG16_SLICES)], str(idx + 1))
-            up.enc[i] = self._conv_params(conv, bn)
-        up.trans_c = self._conv_params(g.trans_c)
-        for i in range(4):
-            u = getattr(g, "up%d" % (i + 1))
-            dc = u.conv.double_conv
-            up.trans_up[i] = self._conv_params(getattr(g, "trans_up%d" % (i + 1)))
-            up.up_t[i] = self._conv_params(u.up)
-            up.up_c1[i] = self._conv_params(getattr(dc, "0"), getattr(dc, "1"))
-            up.up_c2[i] = self._conv_params(getattr(dc, "3"), getattr(dc, "4"))
-        up.outc = self._conv_params(g.outc.conv)
-        up.emds = g.emds.weight.data_ptr()
-        up.n_slices = self.n_slices
-        nb = lib.s3d_unet_packed_bytes(self.n_slices)
-        self._unet_packed = torch.empty(nb, dtype=torch.uint8, device=dev)
-        _lib.check(lib.s3d_unet_pack(C.byref(up), self._unet_packed.data_ptr(), nb, self._stream()), "s3d_unet_pack")
-
-        hp = _lib.S3dHeadParams()
-        hp.fc_p_w, hp.fc_p_b = self.fc_p.weight.data_ptr(), self.fc_p.bias.data_ptr()
-        hp.fc_s_w, hp.fc_s_b = self.fc_s.weight.data_ptr(), self.fc_s.bias.data_ptr()
-        for i, layer in enumerate(self.att_decoder.layers):
-            lp = hp.layer[i]
-            lp.in_proj_w = layer.self_attn.in_proj_weight.data_ptr()
-            lp.in_proj_b = layer.self_attn.in_proj_bias.data_ptr()
-            lp.out_proj_w = layer.self_attn.out_proj.weight.data_ptr()
-            lp.out_proj_b = layer.self_attn.out_proj.bias.data_ptr()
-            lp.lin1_w, lp.lin1_b = layer.linear1.weight.data_ptr(), layer.linear1.bias.data_ptr()
-            lp.lin2_w, lp.lin2_b = layer.linear2.weight.data_ptr(), layer.linear2.bias.data_ptr()
-            lp.norm1_w, lp.norm1_b = layer.norm1.weight.data_ptr(), layer.norm1.bias.data_ptr()
-            lp.norm2_w, lp.norm2_b = layer.norm2.weight.data_ptr(), layer.norm2.bias.data_ptr()
-        hp.fc_out_w, hp.fc_out_b = self.fc_out[0].weight.data_ptr(), self.fc_out[0].bias.data_ptr()
-        nb = lib.s3d_head_packed_bytes()
-        self._head_packed = torch.empty(nb, dtype=torch.uint8, device=dev)
-        _lib.check(lib.s3d_head_pack(C.byref(hp), self._head_packed.data_ptr(), nb, self._stream()), "s3d_head_pack")
-        vp = _lib.S3dVggParams()
-        vgg = self.vggptlossfunc.vgg
-        for i, (idx, _, _) in enumerate(_VGG19_CONVS):
-            vp.conv[i] = self._conv_params(getattr(getattr(vgg, _slice_of(idx, _VGG19_SLICES)), str(idx)))
-        self._vgg_mean = self.vggptlossfunc.mean.reshape(3).contiguous()
-        self._vgg_std = self.vggptlossfunc.std.reshape(3).contiguous()
-        vp.mean, vp.std = self._vgg_mean.data_ptr(), self._vgg_std.data_ptr()
-        nb = lib.s3d_vgg_packed_bytes()
-        self._vgg_packed = torch.empty(nb, dtype=torch.uint8, device=dev)
-        _lib.check(lib.s3d_vgg_pack(C.byref(vp), self._vgg_packed.data_ptr(), nb, self._stream()), "s3d_vgg_pack")
+        self._check_packable()
+        self._unet_packed = self._pack("s3d_unet_pack", unet_params(self, data_ptr),
+                                       lib.s3d_unet_packed_bytes(self.n_slices))
+        self._head_packed = self._pack("s3d_head_pack", head_params(self, data_ptr), lib.s3d_head_packed_bytes())
+        self._vgg_packed = self._pack("s3d_vgg_pack", vgg_params(self, data_ptr), lib.s3d_vgg_packed_bytes())
         self._packed_key = self._params_key()
-
-    def _ensure_packed(self):
-        if self._packed_key is None or self._packed_key != self._params_key():
-            self.repack()
-
-    def _f32(self, t):
-        return t.to(device=self._device(), dtype=torch.float32).contiguous()
 
     def _nhwc_to_nchw(self, t):
         lib = self._require_lib()

@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .models import _VGG16_CFG, _slice_of
+from .models import BN_ALL, HipModel, _VGG16_CFG, _slice_of, conv_params, data_ptr, fill_layers, vgg16_convs
 
 # vgg16bn_feats.py:33-38: torchvision vgg16_bn.features sliced [:4] [4:11] [11:21] [21:31] [31:41] [41:44]
 _GT_SLICES = (("conv1_2", 0, 4), ("conv2_2", 4, 11), ("conv3_3", 11, 21), ("conv4_3", 21, 31),
@@ -52,7 +52,31 @@ class GtLatentCode:
         return lat
 
 
-class Slices3DGTModel(nn.Module):
+def gt_encoder_params(model, pick, last_bn=BN_ALL):
+    """S3dVgg16BnParams of model.img_encoder (see models.py for `pick`).  last_bn: the bn slots conv5_3 (conv[12]) gets
+    from conv_last.41, the BatchNorm of the reference's feat_global, which the regression drops (model_gt.py:77)."""
+    vp = _lib.S3dVgg16BnParams()
+    for i, (conv, bn) in enumerate(vgg16_convs(model.img_encoder, _GT_SLICES)):
+        vp.conv[i] = conv_params(conv, pick, bn, BN_ALL if i < 12 else last_bn)
+    return vp
+
+
+def gt_head_params(model, pick):
+    hp = _lib.S3dGtHeadParams()
+    for k, idx in enumerate((0, 2, 4)):
+        hp.pts_w[k], hp.pts_b[k] = pick(model.pts_feat_extractor[idx].weight), pick(model.pts_feat_extractor[idx].bias)
+    for k, idx in enumerate((0, 2)):
+        hp.local_w[k], hp.local_b[k] = pick(model.fc_local[idx].weight), pick(model.fc_local[idx].bias)
+    fill_layers(hp, model, pick)
+    return hp
+
+
+class Slices3DGTModel(HipModel, nn.Module):
+    _NO_LIB = ("Slices3DGTModel(backend=%r) cannot compute: the HIP library is required (backend='hip'); there is no "
+               "CPU fallback in the product path")
+    _NOT_EVAL = ("Slices3DGTModel computes the eval-mode forward (running-stat BatchNorm, no dropout); "
+                 "call model.eval()")
+
     def __init__(self, img_size=128, n_slices=12, mode="train", backend="hip", prec="f16x3"):
         super().__init__()
         if prec not in ("f32", "f16x3"):
@@ -72,87 +96,19 @@ class Slices3DGTModel(nn.Module):
         self._lib = _lib.load() if backend == "hip" else None
 
     # ------------------------------------------------------------------------------------------
-    def _require_lib(self):
-        if self._lib is None:
-            raise _lib.S3dError("Slices3DGTModel(backend=%r) cannot compute: the HIP library is required "
-                                "(backend='hip'); there is no CPU fallback in the product path" % self.backend)
-        return self._lib
-
-    def _require_eval(self):
-        if self.training:
-            raise RuntimeError("Slices3DGTModel computes the eval-mode forward (running-stat BatchNorm, no dropout); "
-                               "call model.eval()")
-
     def _device(self):
         return self.fc_out[0].weight.device
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self._device()).cuda_stream)
-
-    def _workspace(self, key, nbytes):
-        buf = self._ws.get(key)
-        if buf is None or buf.numel() < nbytes or buf.device != self._device():
-            buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self._device())
-            self._ws[key] = buf
-        return buf
-
-    def _f32(self, t):
-        return t.to(device=self._device(), dtype=torch.float32).contiguous()
-
     def _prec(self):
-        return {"f32": _lib.PREC_F32, "f16x3": _lib.PREC_F16X3, "f16": _lib.PREC_F16}[self.prec]
-
-    def _params_key(self):
-        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
+        return _lib.prec_code(self.prec, ("f32", "f16x3", "f16"))
 
     def repack(self):
         lib = self._require_lib()
-        dev = self._device()
-        if dev.type != "cuda":
-            raise _lib.S3dError("model parameters are on %s; move the model to the GPU (model.cuda())" % dev)
-        for t in list(self.parameters()) + list(self.buffers()):
-            if t.is_floating_point() and (t.dtype != torch.float32 or not t.is_contiguous()):
-                raise _lib.S3dError("parameters must be contiguous fp32")
-        e = self.img_encoder
-        vp = _lib.S3dVgg16BnParams()
-        for i, (idx, _, _) in enumerate(_VGG16_CFG):
-            conv = getattr(getattr(e, _slice_of(idx, _GT_SLICES)), str(idx))
-            bn = getattr(getattr(e, _slice_of(idx + 1, _GT_SLICES)), str(idx + 1))
-            cp = vp.conv[i]
-            cp.w, cp.b = conv.weight.data_ptr(), conv.bias.data_ptr()
-            for k, t in enumerate((bn.weight, bn.bias, bn.running_mean, bn.running_var)):
-                cp.bn[k] = t.data_ptr()
-        nb = lib.s3d_gt_encoder_packed_bytes()
-        self._enc_packed = torch.empty(nb, dtype=torch.uint8, device=dev)
-        _lib.check(lib.s3d_gt_encoder_pack(C.byref(vp), self._enc_packed.data_ptr(), nb, self._stream()),
-                   "s3d_gt_encoder_pack")
-        hp = _lib.S3dGtHeadParams()
-        for k, idx in enumerate((0, 2, 4)):
-            hp.pts_w[k] = self.pts_feat_extractor[idx].weight.data_ptr()
-            hp.pts_b[k] = self.pts_feat_extractor[idx].bias.data_ptr()
-        for k, idx in enumerate((0, 2)):
-            hp.local_w[k] = self.fc_local[idx].weight.data_ptr()
-            hp.local_b[k] = self.fc_local[idx].bias.data_ptr()
-        for i, layer in enumerate(self.att_decoder.layers):
-            lp = hp.layer[i]
-            lp.in_proj_w = layer.self_attn.in_proj_weight.data_ptr()
-            lp.in_proj_b = layer.self_attn.in_proj_bias.data_ptr()
-            lp.out_proj_w = layer.self_attn.out_proj.weight.data_ptr()
-            lp.out_proj_b = layer.self_attn.out_proj.bias.data_ptr()
-            lp.lin1_w, lp.lin1_b = layer.linear1.weight.data_ptr(), layer.linear1.bias.data_ptr()
-            lp.lin2_w, lp.lin2_b = layer.linear2.weight.data_ptr(), layer.linear2.bias.data_ptr()
-            lp.norm1_w, lp.norm1_b = layer.norm1.weight.data_ptr(), layer.norm1.bias.data_ptr()
-            lp.norm2_w, lp.norm2_b = layer.norm2.weight.data_ptr(), layer.norm2.bias.data_ptr()
-        hp.fc_out_w, hp.fc_out_b = self.fc_out[0].weight.data_ptr(), self.fc_out[0].bias.data_ptr()
-        nb = lib.s3d_gt_head_packed_bytes()
-        self._head_packed = torch.empty(nb, dtype=torch.uint8, device=dev)
-        _lib.check(lib.s3d_gt_head_pack(C.byref(hp), self._head_packed.data_ptr(), nb, self._stream()),
-                   "s3d_gt_head_pack")
+        self._check_packable()
+        self._enc_packed = self._pack("s3d_gt_encoder_pack", gt_encoder_params(self, data_ptr),
+                                      lib.s3d_gt_encoder_packed_bytes())
+        self._head_packed = self._pack("s3d_gt_head_pack", gt_head_params(self, data_ptr), lib.s3d_gt_head_packed_bytes())
         self._packed_key = self._params_key()
-
-    def _ensure_packed(self):
-        if self._packed_key is None or self._packed_key != self._params_key():
-            self.repack()
 
     # ------------------------------------------------------------------------------------------
     def encode(self, feed_dict):

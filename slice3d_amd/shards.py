@@ -21,7 +21,6 @@ equal to the reference class on the goldens of tests/test_dataset.py), and write
 (a quarter of the float bytes) — or not at all when the split is cached in HBM (`cache_on_device=True`; 288 GB per
 GPU hold ~100 k samples at 256^2) — and `s3d_dataset_images_fwd` / `s3d_dataset_points_fwd` finish the job on the GPU.
 """
-import ctypes as C
 import json
 import os
 import types
@@ -188,7 +187,7 @@ class ShardLoader:
             self._lib = _lib.load()
         lib, dev = self._lib, self.device
         b, s, ns = len(ids), self.s, self.ns
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        st = _lib.stream_ptr(dev)
         # images: uint8 across PCIe (or already resident), ToTensor + Normalize on the device
         if self._dev_imgs is not None:
             u8 = torch.stack([self._dev_imgs[int(i), int(v)] for i, v in zip(ids, views)])

@@ -10,7 +10,11 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .models import _VGG16_CFG, _VGG16_SLICES, _VGG19_CONVS, _VGG19_SLICES, _slice_of
+from .models import data_ptr, head_params, unet_params, vgg_params
+from .models_gt import gt_encoder_params, gt_head_params
+
+# the batch tensors of a Slices3DRegModel step (the fused step also reads 'sdf')
+_BATCH_KEYS = ("img_input", "img_slices", "qry_norot", "obj_rot_mat", "trans_mat_wo_rot_tp")
 
 
 def bucket_ranges(names, sizes):
@@ -46,7 +50,7 @@ class HipTrainer:
         # "f32": exact fp32 MFMAs; "f16x3": split precision, fp32-class (the headline mode); "f16" (round 6): THROUGHPUT mode — the
         # decoder's GEMM kernels run one f16 MFMA per product, everything else as "f16x3" (fp32 master weights, fp32 accumulation,
         # the same power-of-two backward scale); not fp32-class, reported beside the headline, never instead of it
-        self.prec = {"f32": _lib.PREC_F32, "f16x3": _lib.PREC_F16X3, "f16": _lib.PREC_F16}[prec]
+        self.prec = _lib.prec_code(prec, ("f32", "f16x3", "f16"))
         self.group = process_group
         self.overlap_all_reduce = overlap_all_reduce
         self.sync_bn = sync_bn          # BatchNorm statistics over the batches of all ranks (train.py --sync_bn)
@@ -96,73 +100,14 @@ class HipTrainer:
         att_layer.* twin and down5_.41.* — and vggptlossfunc.* is frozen)."""
         return not (k.startswith("att_layer.") or k.startswith("vggptlossfunc.") or ".down5_." in k)
 
-    # -- struct builders ------------------------------------------------------------------------
+    # -- parameter structs ------------------------------------------------------------------------
     def _gptr(self, t):
         return self._gmap.get(id(t))
 
-    def _conv(self, conv, bn, grad):
-        cp = _lib.S3dConvParams()
-        pick = (lambda t: self._gptr(t)) if grad else (lambda t: t.data_ptr())
-        cp.w = pick(conv.weight)
-        cp.b = pick(conv.bias) if conv.bias is not None else None
-        if bn is not None:
-            cp.bn[0], cp.bn[1] = pick(bn.weight), pick(bn.bias)
-            if not grad:
-                cp.bn[2], cp.bn[3] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-        return cp
-
-    def _unet_struct(self, grad):
-        g = self.model.slices_generator
-        up = _lib.S3dUNetParams()
-        seqs = {name: getattr(g, name) for name, _, _ in _VGG16_SLICES}
-        for i, (idx, _, _) in enumerate(_VGG16_CFG):
-            conv = getattr(seqs[_slice_of(idx, _VGG16_SLICES)], str(idx))
-            bn = getattr(seqs[_slice_of(idx + 1, _VGG16_SLICES)], str(idx + 1)) if i < 12 else None
-            up.enc[i] = self._conv(conv, bn, grad)
-        up.trans_c = self._conv(g.trans_c, None, grad)
-        for i in range(4):
-            u = getattr(g, "up%d" % (i + 1))
-            dc = u.conv.double_conv
-            up.trans_up[i] = self._conv(getattr(g, "trans_up%d" % (i + 1)), None, grad)
-            up.up_t[i] = self._conv(u.up, None, grad)
-            up.up_c1[i] = self._conv(getattr(dc, "0"), getattr(dc, "1"), grad)
-            up.up_c2[i] = self._conv(getattr(dc, "3"), getattr(dc, "4"), grad)
-        up.outc = self._conv(g.outc.conv, None, grad)
-        up.emds = self._gptr(g.emds.weight) if grad else g.emds.weight.data_ptr()
-        up.n_slices = self.model.n_slices
-        return up
-
-    def _fill_layers(self, hp, pick):
-        m = self.model
-        for i, layer in enumerate(m.att_decoder.layers):
-            lp = hp.layer[i]
-            lp.in_proj_w, lp.in_proj_b = pick(layer.self_attn.in_proj_weight), pick(layer.self_attn.in_proj_bias)
-            lp.out_proj_w, lp.out_proj_b = pick(layer.self_attn.out_proj.weight), pick(layer.self_attn.out_proj.bias)
-            lp.lin1_w, lp.lin1_b = pick(layer.linear1.weight), pick(layer.linear1.bias)
-            lp.lin2_w, lp.lin2_b = pick(layer.linear2.weight), pick(layer.linear2.bias)
-            lp.norm1_w, lp.norm1_b = pick(layer.norm1.weight), pick(layer.norm1.bias)
-            lp.norm2_w, lp.norm2_b = pick(layer.norm2.weight), pick(layer.norm2.bias)
-        hp.fc_out_w, hp.fc_out_b = pick(m.fc_out[0].weight), pick(m.fc_out[0].bias)
-
-    def _head_struct(self, grad):
-        m = self.model
-        pick = (lambda t: self._gptr(t)) if grad else (lambda t: t.data_ptr())
-        hp = _lib.S3dHeadParams()
-        hp.fc_p_w, hp.fc_p_b = pick(m.fc_p.weight), pick(m.fc_p.bias)
-        hp.fc_s_w, hp.fc_s_b = pick(m.fc_s.weight), pick(m.fc_s.bias)
-        self._fill_layers(hp, pick)
-        return hp
-
-    def _vgg_struct(self):
-        vp = _lib.S3dVggParams()
-        vgg = self.model.vggptlossfunc.vgg
-        for i, (idx, _, _) in enumerate(_VGG19_CONVS):
-            conv = getattr(getattr(vgg, _slice_of(idx, _VGG19_SLICES)), str(idx))
-            vp.conv[i].w, vp.conv[i].b = conv.weight.data_ptr(), conv.bias.data_ptr()
-        self._mean = self.model.vggptlossfunc.mean.reshape(3).contiguous()
-        self._std = self.model.vggptlossfunc.std.reshape(3).contiguous()
-        vp.mean, vp.std = self._mean.data_ptr(), self._std.data_ptr()
-        return vp
+    def _structs(self, pick):
+        """U-Net and head structs of the step (values: pick = data_ptr, gradients: pick = self._gptr).  The step does
+        not run down5_.41, the BatchNorm of the reference's unused x5_: conv5_3 carries no BatchNorm."""
+        return unet_params(self.model, pick, last_bn=()), head_params(self.model, pick)
 
     def _next_seed(self):
         """Fresh dropout seed per call (rank-dependent so data-parallel ranks draw different masks)."""
@@ -176,51 +121,49 @@ class HipTrainer:
         [loss_pred, loss_img, loss_vgg, acc] (and sdf_pred / slices_rec if asked)."""
         m, lib = self.model, self.lib
         dev = self.grad_flat.device
-        f = lambda k: batch[k].to(device=dev, dtype=torch.float32).contiguous()
-        img, sl, qry, rot, tm, sdf = (f(k) for k in ("img_input", "img_slices", "qry_norot", "obj_rot_mat",
-                                                       "trans_mat_wo_rot_tp", "sdf"))
-        b, _, s, _ = img.shape
-        q, ns = qry.shape[1], m.n_slices
-        tb = _lib.S3dTrainBatch()
-        tb.img, tb.img_slices, tb.qry = img.data_ptr(), sl.data_ptr(), qry.data_ptr()
-        tb.rot, tb.trans, tb.sdf = rot.data_ptr(), tm.data_ptr(), sdf.data_ptr()
-        if self.overlap_all_reduce and self._exchange_on():
-            for k, e in enumerate(self._ddp_events()):
-                tb.ev_grad_ready[k] = e.cuda_event
-            self._events_armed = True
-        self._attach_sync(tb)
-        self._workspace(b, s, q, ns)
+        t = self._batch(batch, _BATCH_KEYS + ("sdf",))
+        b, _, s, _ = t["img_input"].shape
+        q, ns = t["qry_norot"].shape[1], m.n_slices
+        tb = self._batch_struct(t, arm_events=True)
+        self._workspace(lib.s3d_train_workspace_bytes(b, s, q, ns))
         sdf_pred = torch.empty((b, q), dtype=torch.float32, device=dev) if want_outputs else None
         rec = torch.empty((b * ns, 3, s, s), dtype=torch.float32, device=dev) if want_outputs else None
-        u, h, v = self._unet_struct(False), self._head_struct(False), self._vgg_struct()
-        du, dh = self._unet_struct(True), self._head_struct(True)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        (u, h), v = self._structs(data_ptr), vgg_params(m, data_ptr)
+        du, dh = self._structs(self._gptr)
         _lib.check(lib.s3d_train_fwd_bwd(C.byref(u), C.byref(h), C.byref(v), C.byref(du), C.byref(dh), C.byref(tb),
                                          b, s, q, ns, float(self.dropout), self._next_seed(), self.prec,
                                          self._losses.data_ptr(),
                                          sdf_pred.data_ptr() if want_outputs else None,
                                          rec.data_ptr() if want_outputs else None,
-                                         self._ws.data_ptr(), self._ws.numel(), stream), "s3d_train_fwd_bwd")
+                                         self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr(dev)),
+                   "s3d_train_fwd_bwd")
         m._packed_key = None   # BN running statistics changed in place: eval-mode packs are stale
         if want_outputs:
             return self._losses, sdf_pred, rec.view(b, ns * 3, s, s)
         return self._losses
 
     # -- autograd-style halves of the step (s3d_train_fwd / s3d_train_bwd) ----------------------------
-    def _batch_struct(self, batch, need_sdf):
+    def _batch(self, batch, keys):
+        """The batch tensors `keys` as contiguous fp32 on the trainer's device."""
         dev = self.grad_flat.device
-        f = lambda k: batch[k].to(device=dev, dtype=torch.float32).contiguous()
-        keys = ["img_input", "img_slices", "qry_norot", "obj_rot_mat", "trans_mat_wo_rot_tp"] + (["sdf"] if need_sdf else [])
-        t = {k: f(k) for k in keys}
-        tb = _lib.S3dTrainBatch()
-        tb.img, tb.img_slices, tb.qry = t["img_input"].data_ptr(), t["img_slices"].data_ptr(), t["qry_norot"].data_ptr()
-        tb.rot, tb.trans = t["obj_rot_mat"].data_ptr(), t["trans_mat_wo_rot_tp"].data_ptr()
-        tb.sdf = t["sdf"].data_ptr() if need_sdf else None
-        self._attach_sync(tb)
-        return tb, t
+        return {k: batch[k].to(device=dev, dtype=torch.float32).contiguous() for k in keys}
 
-    def _workspace(self, b, s, q, ns):
-        nb = self.lib.s3d_train_workspace_bytes(b, s, q, ns)
+    def _batch_struct(self, t, arm_events=False):
+        """S3dTrainBatch of the tensors `t` (from _batch; a missing key is NULL) + the sync-BN hook; arm_events: the
+        bucket events of the overlapped all-reduce, when the step exchanges gradients."""
+        tb = _lib.S3dTrainBatch()
+        for field, k in (("img", "img_input"), ("img_slices", "img_slices"), ("qry", "qry_norot"), ("rot", "obj_rot_mat"),
+                         ("trans", "trans_mat_wo_rot_tp"), ("sdf", "sdf")):
+            if k in t:
+                setattr(tb, field, t[k].data_ptr())
+        if arm_events and self.overlap_all_reduce and self._exchange_on():
+            for k, e in enumerate(self._ddp_events()):
+                tb.ev_grad_ready[k] = e.cuda_event
+            self._events_armed = True
+        self._attach_sync(tb)
+        return tb
+
+    def _workspace(self, nb):
         if self._ws is None or self._ws.numel() < nb:
             self._ws = None                      # release before growing (tens of GB at full size)
             self._ws = torch.empty(nb, dtype=torch.uint8, device=self.grad_flat.device)
@@ -231,19 +174,19 @@ class HipTrainer:
         (sdf_pred (B,Q), slices_rec (B,3*ns,S,S), vgg_loss ()) and a context for backward_from; every activation the
         backward needs stays in this trainer's workspace until the next forward."""
         m, lib, dev = self.model, self.lib, self.grad_flat.device
-        tb, t = self._batch_struct(batch, need_sdf=False)
+        t = self._batch(batch, _BATCH_KEYS)
+        tb = self._batch_struct(t)
         b, _, s, _ = t["img_input"].shape
         q, ns = t["qry_norot"].shape[1], m.n_slices
-        ws = self._workspace(b, s, q, ns)
+        ws = self._workspace(lib.s3d_train_workspace_bytes(b, s, q, ns))
         sdf_pred = torch.empty((b, q), dtype=torch.float32, device=dev)
         rec = torch.empty((b * ns, 3, s, s), dtype=torch.float32, device=dev)
         vgg = torch.empty((), dtype=torch.float32, device=dev)
         seed = self._next_seed()
-        u, h, v = self._unet_struct(False), self._head_struct(False), self._vgg_struct()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        (u, h), v = self._structs(data_ptr), vgg_params(m, data_ptr)
         _lib.check(lib.s3d_train_fwd(C.byref(u), C.byref(h), C.byref(v), C.byref(tb), b, s, q, ns, float(self.dropout),
                                      seed, self.prec, vgg.data_ptr(), sdf_pred.data_ptr(), rec.data_ptr(),
-                                     ws.data_ptr(), ws.numel(), stream), "s3d_train_fwd")
+                                     ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "s3d_train_fwd")
         m._packed_key = None   # BN running statistics changed in place: eval-mode packs are stale
         ctx = {"t": t, "dims": (b, s, q, ns), "seed": seed, "rec": rec, "dropout": float(self.dropout)}
         self._last_ctx = ctx
@@ -265,23 +208,18 @@ class HipTrainer:
     def backward_from(self, ctx, d_sdf=None, d_rec=None, d_vgg=0.0, grad_scale=0.0):
         """Backward of forward_only from the output gradients; WRITES the parameter gradients into grad_flat
         (param.grad views when bind_grads).  grad_scale: see s3d_train_bwd (0 = automatic)."""
-        lib, dev = self.lib, self.grad_flat.device
+        m, lib, dev = self.model, self.lib, self.grad_flat.device
         b, s, q, ns = ctx["dims"]
-        t = ctx["t"]
-        tb = _lib.S3dTrainBatch()
-        tb.img, tb.img_slices, tb.qry = t["img_input"].data_ptr(), t["img_slices"].data_ptr(), t["qry_norot"].data_ptr()
-        tb.rot, tb.trans = t["obj_rot_mat"].data_ptr(), t["trans_mat_wo_rot_tp"].data_ptr()
-        self._attach_sync(tb)
+        tb = self._batch_struct(ctx["t"])
         g = lambda x, shape: None if x is None else x.to(device=dev, dtype=torch.float32).reshape(shape).contiguous()
         d_sdf, d_rec = g(d_sdf, (b, q)), g(d_rec, (b * ns, 3, s, s))
-        u, h, v = self._unet_struct(False), self._head_struct(False), self._vgg_struct()
-        du, dh = self._unet_struct(True), self._head_struct(True)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        (u, h), v = self._structs(data_ptr), vgg_params(m, data_ptr)
+        du, dh = self._structs(self._gptr)
         _lib.check(lib.s3d_train_bwd(C.byref(u), C.byref(h), C.byref(v), C.byref(du), C.byref(dh), C.byref(tb), b, s, q,
                                      ns, ctx["dropout"], ctx["seed"], self.prec,
                                      d_sdf.data_ptr() if d_sdf is not None else None,
                                      d_rec.data_ptr() if d_rec is not None else None, float(d_vgg), float(grad_scale),
-                                     ctx["rec"].data_ptr(), self._ws.data_ptr(), self._ws.numel(), stream),
+                                     ctx["rec"].data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr(dev)),
                    "s3d_train_bwd")
         return self.grad_flat
 
@@ -384,14 +322,14 @@ class HipTrainer:
 
     def adam_step(self):
         self.step += 1
-        stream = C.c_void_p(torch.cuda.current_stream(self.grad_flat.device).cuda_stream)
         n = len(self.params)
         ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in self.params])
         offs = (C.c_long * n)(*[self.offsets[k] for k in self.names])
         sizes = (C.c_long * n)(*[p.numel() for p in self.params])
         _lib.check(self.lib.s3d_adam_step_multi(ptrs, offs, sizes, n, self.grad_flat.data_ptr(), self.exp_avg.data_ptr(),
                                                 self.exp_avg_sq.data_ptr(), self.lr, self.betas[0], self.betas[1],
-                                                self.eps, self.step, stream), "s3d_adam_step_multi")
+                                                self.eps, self.step, _lib.stream_ptr(self.grad_flat.device)),
+                   "s3d_adam_step_multi")
         self.model._packed_key = None
 
     def state_dict(self):
@@ -461,60 +399,33 @@ class HipGtTrainer(HipTrainer):
         dead = ("att_layer.", "fc_global.", "img_encoder.classifier.", "img_encoder.conv_last.")
         return not k.startswith(dead)
 
-    def _enc_struct(self, grad):
-        from .models_gt import _GT_SLICES
-        e = self.model.img_encoder
-        vp = _lib.S3dVgg16BnParams()
-        for i, (idx, _, _) in enumerate(_VGG16_CFG):
-            conv = getattr(getattr(e, _slice_of(idx, _GT_SLICES)), str(idx))
-            bn = getattr(getattr(e, _slice_of(idx + 1, _GT_SLICES)), str(idx + 1))
-            if i < 12:
-                vp.conv[i] = self._conv(conv, bn, grad)
-            else:   # conv5_3's BatchNorm (conv_last.41): running statistics move, weight / bias get no gradient
-                vp.conv[i] = self._conv(conv, None, grad)
-                if not grad:
-                    vp.conv[i].bn[2], vp.conv[i].bn[3] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-        return vp
-
-    def _gt_head_struct(self, grad):
-        m = self.model
-        pick = (lambda t: self._gptr(t)) if grad else (lambda t: t.data_ptr())
-        hp = _lib.S3dGtHeadParams()
-        for k, idx in enumerate((0, 2, 4)):
-            hp.pts_w[k], hp.pts_b[k] = pick(m.pts_feat_extractor[idx].weight), pick(m.pts_feat_extractor[idx].bias)
-        for k, idx in enumerate((0, 2)):
-            hp.local_w[k], hp.local_b[k] = pick(m.fc_local[idx].weight), pick(m.fc_local[idx].bias)
-        self._fill_layers(hp, pick)
-        return hp
+    def _structs(self, pick):
+        """Encoder and head structs of the step.  conv_last.41 (the BatchNorm of the reference's feat_global, dropped by
+        model_gt.py:77) gets its running statistics, which the step moves as the reference's forward does, and no weight /
+        bias: its output is unused."""
+        return gt_encoder_params(self.model, pick, last_bn=(2, 3)), gt_head_params(self.model, pick)
 
     def forward_backward(self, batch, want_outputs=False):
         """Train-mode forward + L1 loss + backward; fills param.grad.  Returns the device tensor
         [loss_pred, acc, 0, 0] (and sdf_pred if asked)."""
         m, lib = self.model, self.lib
         dev = self.grad_flat.device
-        f = lambda k: batch[k].to(device=dev, dtype=torch.float32).contiguous()
-        sl, qry, rot, tm, sdf = (f(k) for k in ("img_slices", "qry_norot", "obj_rot_mat", "trans_mat_wo_rot_tp",
-                                                  "sdf"))
-        b, c, s, _ = sl.shape
-        q, ns = qry.shape[1], m.n_slices
+        t = self._batch(batch, ("img_slices", "qry_norot", "obj_rot_mat", "trans_mat_wo_rot_tp", "sdf"))
+        b, c, s, _ = t["img_slices"].shape
+        q, ns = t["qry_norot"].shape[1], m.n_slices
         if c != 3 * ns:
             raise ValueError("img_slices has %d channels, expected 3*n_slices = %d" % (c, 3 * ns))
-        tb = _lib.S3dTrainBatch()
-        tb.img_slices, tb.qry = sl.data_ptr(), qry.data_ptr()
-        tb.rot, tb.trans, tb.sdf = rot.data_ptr(), tm.data_ptr(), sdf.data_ptr()
-        self._attach_sync(tb)
-        nb = lib.s3d_gt_train_workspace_bytes(b, s, q, ns)
-        if self._ws is None or self._ws.numel() < nb:
-            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        tb = self._batch_struct(t)
+        self._workspace(lib.s3d_gt_train_workspace_bytes(b, s, q, ns))
         sdf_pred = torch.empty((b, q), dtype=torch.float32, device=dev) if want_outputs else None
-        e, h = self._enc_struct(False), self._gt_head_struct(False)
-        de, dh = self._enc_struct(True), self._gt_head_struct(True)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        e, h = self._structs(data_ptr)
+        de, dh = self._structs(self._gptr)
         _lib.check(lib.s3d_gt_train_fwd_bwd(C.byref(e), C.byref(h), C.byref(de), C.byref(dh), C.byref(tb),
                                             b, s, q, ns, float(self.dropout), self._next_seed(), self.prec,
                                             self._losses.data_ptr(),
                                             sdf_pred.data_ptr() if want_outputs else None,
-                                            self._ws.data_ptr(), self._ws.numel(), stream), "s3d_gt_train_fwd_bwd")
+                                            self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr(dev)),
+                   "s3d_gt_train_fwd_bwd")
         m._packed_key = None   # BN running statistics changed in place: eval-mode packs are stale
         if want_outputs:
             return self._losses, sdf_pred
