@@ -240,8 +240,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(const ConvLaunc
 // split-precision variant: same tiling, 32-deep K chunks, A = pre-packed f16 hi/lo fragment pairs,
 // B = fp32 activations split into hi/lo on the fly, 3 f16 MFMAs per product (see decode_f16.hip).
 // ---------------------------------------------------------------------------------------------
-typedef _Float16 chalf8 __attribute__((ext_vector_type(8)));
-
 template <int MT, int NT, int WM, int WN, int KS>
 __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_f16x3_kernel(const ConvLaunch a) {
     const int lane = threadIdx.x & 63;
@@ -304,7 +302,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_f16x3_kernel(const Con
             // chunk's loads before this chunk's MFMAs (two register sets, the loop unrolled by two): one chunk per L2 round
             // trip made the small GEMMs of the LDM U-Net at batch 1 (32 x 32-pixel tiles, 20 chunks, 2.5 waves per SIMD) pure
             // latency — 15 us for 1.3 GMAC.
-            auto issue = [&](int c, f32x4 (&v0)[MT], f32x4 (&v1)[MT], chalf8 (&wh)[NT], chalf8 (&wl)[NT]) {
+            auto issue = [&](int c, f32x4 (&v0)[MT], f32x4 (&v1)[MT], s3d_half8 (&wh)[NT], s3d_half8 (&wl)[NT]) {
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
                     v0[mt] = ok[mt] ? ld4(bp[mt] + 32 * c) : zero4();
@@ -313,12 +311,12 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_f16x3_kernel(const Con
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     const _Float16* f = wp + ((size_t)nt * KU32 + c) * 1024;
-                    wh[nt] = *reinterpret_cast<const chalf8*>(f);
-                    wl[nt] = *reinterpret_cast<const chalf8*>(f + 512);
+                    wh[nt] = *reinterpret_cast<const s3d_half8*>(f);
+                    wl[nt] = *reinterpret_cast<const s3d_half8*>(f + 512);
                 }
             };
-            auto consume = [&](const f32x4 (&v0)[MT], const f32x4 (&v1)[MT], const chalf8 (&wh)[NT], const chalf8 (&wl)[NT]) {
-                chalf8 bh[MT], bl[MT];
+            auto consume = [&](const f32x4 (&v0)[MT], const f32x4 (&v1)[MT], const s3d_half8 (&wh)[NT], const s3d_half8 (&wl)[NT]) {
+                s3d_half8 bh[MT], bl[MT];
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
@@ -345,10 +343,10 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_f16x3_kernel(const Con
                 }
             };
             f32x4 p0[MT], p1[MT];
-            chalf8 pwh[NT], pwl[NT];
+            s3d_half8 pwh[NT], pwl[NT];
             if constexpr (MT * NT <= 8) {   // (the 4 x 4 tile would need 300 registers for two sets: it has the MFMA work to cover a round trip)
                 f32x4 q0[MT], q1[MT];
-                chalf8 qwh[NT], qwl[NT];
+                s3d_half8 qwh[NT], qwl[NT];
                 issue(0, p0, p1, pwh, pwl);
                 int c = 0;
 #pragma unroll 1
@@ -421,7 +419,7 @@ __global__ __launch_bounds__(256, 2) void lin_rows_f16x3_kernel(const ConvLaunch
     for (int mt = 0; mt < LR_MT; ++mt)
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            chalf8 h, l;
+            s3d_half8 h, l;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const _Float16 h0 = (_Float16)v0[mt][u][t], h1 = (_Float16)v1[mt][u][t];
@@ -432,8 +430,8 @@ __global__ __launch_bounds__(256, 2) void lin_rows_f16x3_kernel(const ConvLaunch
             v0[mt][u] = __builtin_bit_cast(f32x4, h);
             v1[mt][u] = __builtin_bit_cast(f32x4, l);
         }
-#define LR_XH(mt, u) __builtin_bit_cast(chalf8, v0[mt][u])
-#define LR_XL(mt, u) __builtin_bit_cast(chalf8, v1[mt][u])
+#define LR_XH(mt, u) __builtin_bit_cast(s3d_half8, v0[mt][u])
+#define LR_XL(mt, u) __builtin_bit_cast(s3d_half8, v1[mt][u])
     const int n_jt = a.CoutPad >> 4;
 #pragma unroll 1
     for (int jt = 0; jt < n_jt; jt += 2) {
@@ -441,11 +439,11 @@ __global__ __launch_bounds__(256, 2) void lin_rows_f16x3_kernel(const ConvLaunch
 #pragma unroll
         for (int mt = 0; mt < LR_MT; ++mt) acc[mt][0] = acc[mt][1] = zero4();
         const _Float16* wp = wimg + (size_t)jt * KU32 * 1024 + lane * 8;
-        chalf8 wh[2][2], wl[2][2];   // [buffer][nt]: the next k-step's fragments are requested before this one's MFMAs
+        s3d_half8 wh[2][2], wl[2][2];   // [buffer][nt]: the next k-step's fragments are requested before this one's MFMAs
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-            wh[0][nt] = *reinterpret_cast<const chalf8*>(wp + (size_t)nt * KU32 * 1024);
-            wl[0][nt] = *reinterpret_cast<const chalf8*>(wp + (size_t)nt * KU32 * 1024 + 512);
+            wh[0][nt] = *reinterpret_cast<const s3d_half8*>(wp + (size_t)nt * KU32 * 1024);
+            wl[0][nt] = *reinterpret_cast<const s3d_half8*>(wp + (size_t)nt * KU32 * 1024 + 512);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -454,8 +452,8 @@ __global__ __launch_bounds__(256, 2) void lin_rows_f16x3_kernel(const ConvLaunch
 #pragma unroll
                     for (int nt = 0; nt < 2; ++nt) {
                         const _Float16* f = wp + ((size_t)nt * KU32 + u + 1) * 1024;
-                        wh[(u + 1) & 1][nt] = *reinterpret_cast<const chalf8*>(f);
-                        wl[(u + 1) & 1][nt] = *reinterpret_cast<const chalf8*>(f + 512);
+                        wh[(u + 1) & 1][nt] = *reinterpret_cast<const s3d_half8*>(f);
+                        wl[(u + 1) & 1][nt] = *reinterpret_cast<const s3d_half8*>(f + 512);
                     }
                 }
 #pragma unroll
@@ -510,12 +508,10 @@ static int launch_lin_rows(const ConvLaunch& a, hipStream_t stream) {
 // stores of the phase before have retired — whatever their number (tail rows store nothing) — before the wave arrives
 // at the next barrier; the stores of this phase get a whole phase to retire.  LDS is read by hand-issued ds_read_b128
 // with counted lgkmcnt waits only (no compiler-visible LDS access: nothing makes hipcc guard them with vmcnt(0)).
-// Per accumulator the products are added in the order of lin_rows / conv_igemm_f16x3 (k ascending; hi*lo, lo*hi, hi*hi):
+// Per accumulator the products are added in the order of lin_rows / conv_igemm_f16x3 (k ascending; s3d_mfma3's product order):
 // the same bits.
 // ---------------------------------------------------------------------------------------------
 #define LS_SLOT_HALFS 8192
-#define LS_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-#define LS_WAIT4(n, a, b, c, d) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(n))
 #define LS_GLOAD(dst, ptr) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(ptr) : "memory")
 // the epilogue of conv_epilogue restricted to what these calls use (bias, ReLU, output dropout, residual; NHWC rows:
 // the output index is the flat row index times the channel stride) — the general one costs 50 registers more
@@ -570,14 +566,8 @@ __global__ __launch_bounds__(256, 2) void lin_stream_f16x3_kernel(const ConvLaun
     // image and in the slot (fragment f = 4 nt + u at f * 2 KiB)
     auto dma_slot = [&](int q, int slot) {   // q = kc * n_slots + ns: phase within a task
         const int kc = KC > 1 ? q >> 2 : 0, ns = KC > 1 ? q & 3 : q;
-        const __attribute__((address_space(1))) void* gp = (const __attribute__((address_space(1))) void*)(
-            wimg + ((size_t)(2 * ns + (wave >> 1)) * KU32 + 4 * kc + 2 * (wave & 1)) * 1024 + lane * 8);
-        __attribute__((address_space(3))) void* lp =
-            (__attribute__((address_space(3))) void*)(s_w + slot * LS_SLOT_HALFS + wave * 2048);
-        __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds(gp, lp, 16, 1024, 0);
-        __builtin_amdgcn_global_load_lds(gp, lp, 16, 2048, 0);
-        __builtin_amdgcn_global_load_lds(gp, lp, 16, 3072, 0);
+        s3d_dma_pieces<4>(wimg + ((size_t)(2 * ns + (wave >> 1)) * KU32 + 4 * kc + 2 * (wave & 1)) * 1024 + lane * 8,
+                          s_w + slot * LS_SLOT_HALFS + wave * 2048);
     };
     int slot = 0, q = 0;   // ring slot and task phase of the NEXT phase to run
     dma_slot(0, 0);
@@ -623,8 +613,8 @@ __global__ __launch_bounds__(256, 2) void lin_stream_f16x3_kernel(const ConvLaun
                     v0[mt][u] = __builtin_bit_cast(f32x4, h);
                     v1[mt][u] = __builtin_bit_cast(f32x4, l);
                 }
-#define LS_XH(mt, u) __builtin_bit_cast(chalf8, v0[mt][u])
-#define LS_XL(mt, u) __builtin_bit_cast(chalf8, v1[mt][u])
+#define LS_XH(mt, u) __builtin_bit_cast(s3d_half8, v0[mt][u])
+#define LS_XL(mt, u) __builtin_bit_cast(s3d_half8, v1[mt][u])
             if (first) {   // the two prologue slots
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 first = false;
@@ -671,12 +661,12 @@ __global__ __launch_bounds__(256, 2) void lin_stream_f16x3_kernel(const ConvLaun
                     }
                     __builtin_amdgcn_sched_barrier(0);
                     const unsigned lwa = lw0 + (unsigned)slot * (LS_SLOT_HALFS * 2);
-                    chalf8 wh[2][2], wl[2][2];   // [buffer][nt]
+                    s3d_half8 wh[2][2], wl[2][2];   // [buffer][nt]
 #define LS_READS(B, U)                                  \
-    LS_READ(wh[B][0], lwa, (U) * 2048);                 \
-    LS_READ(wl[B][0], lwa, (U) * 2048 + 1024);          \
-    LS_READ(wh[B][1], lwa, (4 + (U)) * 2048);           \
-    LS_READ(wl[B][1], lwa, (4 + (U)) * 2048 + 1024);
+    S3D_DS_READ(wh[B][0], lwa, (U) * 2048);                 \
+    S3D_DS_READ(wl[B][0], lwa, (U) * 2048 + 1024);          \
+    S3D_DS_READ(wh[B][1], lwa, (4 + (U)) * 2048);           \
+    S3D_DS_READ(wl[B][1], lwa, (4 + (U)) * 2048 + 1024);
 #define LS_MFMA(B, U)                                                                                                  \
     _Pragma("unroll") for (int nt = 0; nt < 2; ++nt) {                                                                 \
         if (!a.single_pass) {                                                                                          \
@@ -694,15 +684,15 @@ __global__ __launch_bounds__(256, 2) void lin_stream_f16x3_kernel(const ConvLaun
     __builtin_amdgcn_sched_barrier(0);
                     LS_READS(0, 0)
                     LS_READS(1, 1)
-                    LS_WAIT4(4, wh[0][0], wl[0][0], wh[0][1], wl[0][1]);
+                    S3D_LGKM_WAIT4(4, wh[0][0], wl[0][0], wh[0][1], wl[0][1]);
                     LS_MFMA(0, 0)
                     LS_READS(0, 2)
-                    LS_WAIT4(4, wh[1][0], wl[1][0], wh[1][1], wl[1][1]);
+                    S3D_LGKM_WAIT4(4, wh[1][0], wl[1][0], wh[1][1], wl[1][1]);
                     LS_MFMA(1, 1)
                     LS_READS(1, 3)
-                    LS_WAIT4(4, wh[0][0], wl[0][0], wh[0][1], wl[0][1]);
+                    S3D_LGKM_WAIT4(4, wh[0][0], wl[0][0], wh[0][1], wl[0][1]);
                     LS_MFMA(0, 2)
-                    LS_WAIT4(0, wh[1][0], wl[1][0], wh[1][1], wl[1][1]);
+                    S3D_LGKM_WAIT4(0, wh[1][0], wl[1][0], wh[1][1], wl[1][1]);
                     LS_MFMA(1, 3)
 #undef LS_READS
 #undef LS_MFMA
@@ -857,7 +847,6 @@ __global__ __launch_bounds__(256) void conv3x3_lds_f16x3_kernel(const ConvLaunch
         }
     };
     auto park = [&](int buf) {
-        typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
 #pragma unroll
         for (int i = 0; i < NPRE; ++i) {
             const int slot = threadIdx.x + 256 * i;
@@ -873,7 +862,7 @@ __global__ __launch_bounds__(256) void conv3x3_lds_f16x3_kernel(const ConvLaunch
                     }
                     pre[i] = (pre_ok >> i) & 1u ? t : zero4();
                 }
-                half4_t hi, lo;
+                s3d_half4 hi, lo;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const _Float16 h = (_Float16)pre[i][t];
@@ -881,8 +870,8 @@ __global__ __launch_bounds__(256) void conv3x3_lds_f16x3_kernel(const ConvLaunch
                     lo[t] = (_Float16)(pre[i][t] - (float)h);
                 }
                 const int po = pix * C3_PXS + C3_SWZ(pix, q4 >> 1) + 4 * (q4 & 1);
-                *reinterpret_cast<half4_t*>(&s_in[buf][0][po]) = hi;
-                *reinterpret_cast<half4_t*>(&s_in[buf][1][po]) = lo;
+                *reinterpret_cast<s3d_half4*>(&s_in[buf][0][po]) = hi;
+                *reinterpret_cast<s3d_half4*>(&s_in[buf][1][po]) = lo;
             }
         }
     };
@@ -913,12 +902,12 @@ __global__ __launch_bounds__(256) void conv3x3_lds_f16x3_kernel(const ConvLaunch
         const int ubase = s ? 9 * cu0 : 0;
         const _Float16* wp0 = wimg + ((size_t)jt0 * KU32 + ubase + c) * 1024 + lane * 8;   // + tap*cu*1024, + nt*KU32*1024
         // weight fragments of tap 0 are requested BEFORE the halo prefetch (vmcnt retires in order)
-        chalf8 wh[NT], wl[NT];
+        s3d_half8 wh[NT], wl[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const _Float16* f = wp0 + (size_t)nt * KU32 * 1024;
-            wh[nt] = *reinterpret_cast<const chalf8*>(f);
-            wl[nt] = *reinterpret_cast<const chalf8*>(f + 512);
+            wh[nt] = *reinterpret_cast<const s3d_half8*>(f);
+            wl[nt] = *reinterpret_cast<const s3d_half8*>(f + 512);
         }
         if (ch + 1 < nchunk) {
             const int s1 = ch + 1 < cu0 ? 0 : 1;
@@ -929,22 +918,22 @@ __global__ __launch_bounds__(256) void conv3x3_lds_f16x3_kernel(const ConvLaunch
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int dy = tap / 3, dx = tap % 3;   // halo-relative: output (r, m) reads halo (r + dy, m + dx)
-            chalf8 nwh[NT], nwl[NT];
+            s3d_half8 nwh[NT], nwl[NT];
             if (tap < 8) {
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     const _Float16* f = wp0 + ((size_t)nt * KU32 + (size_t)(tap + 1) * cu) * 1024;
-                    nwh[nt] = *reinterpret_cast<const chalf8*>(f);
-                    nwl[nt] = *reinterpret_cast<const chalf8*>(f + 512);
+                    nwh[nt] = *reinterpret_cast<const s3d_half8*>(f);
+                    nwl[nt] = *reinterpret_cast<const s3d_half8*>(f + 512);
                 }
             }
-            chalf8 bh[MT], bl[MT];
+            s3d_half8 bh[MT], bl[MT];
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 const int pix = (MT * wp + mt + dy) * 18 + m + dx;
                 const int po = pix * C3_PXS + C3_SWZ(pix, g);
-                bh[mt] = *reinterpret_cast<const chalf8*>(sh + po);
-                bl[mt] = *reinterpret_cast<const chalf8*>(sl + po);
+                bh[mt] = *reinterpret_cast<const s3d_half8*>(sh + po);
+                bl[mt] = *reinterpret_cast<const s3d_half8*>(sl + po);
             }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
@@ -1116,7 +1105,6 @@ __global__ __launch_bounds__(256) void conv3x3_small_f16x3_kernel(const ConvLaun
         }
     };
     auto park = [&](int buf) {
-        typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
 #pragma unroll
         for (int i = 0; i < NPRE; ++i) {
             const int slot = threadIdx.x + 256 * i;
@@ -1132,7 +1120,7 @@ __global__ __launch_bounds__(256) void conv3x3_small_f16x3_kernel(const ConvLaun
                     }
                     pre[i] = (pre_ok >> i) & 1u ? t : zero4();
                 }
-                half4_t hi, lo;
+                s3d_half4 hi, lo;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const _Float16 h = (_Float16)pre[i][t];
@@ -1140,8 +1128,8 @@ __global__ __launch_bounds__(256) void conv3x3_small_f16x3_kernel(const ConvLaun
                     lo[t] = (_Float16)(pre[i][t] - (float)h);
                 }
                 const int po = pix * C3_PXS + C3_SWZ(pix, q4 >> 1) + 4 * (q4 & 1);
-                *reinterpret_cast<half4_t*>(&s_in[buf][0][po]) = hi;
-                *reinterpret_cast<half4_t*>(&s_in[buf][1][po]) = lo;
+                *reinterpret_cast<s3d_half4*>(&s_in[buf][0][po]) = hi;
+                *reinterpret_cast<s3d_half4*>(&s_in[buf][1][po]) = lo;
             }
         }
     };
@@ -1149,14 +1137,14 @@ __global__ __launch_bounds__(256) void conv3x3_small_f16x3_kernel(const ConvLaun
     const int ch_lo = blockIdx.y * chunks_per_split;
     const int nchunk = min(cu0 + cu1, ch_lo + chunks_per_split);
     constexpr bool DBW = PT == 1;   // the next chunk's weights under this chunk's products (144 registers); PT >= 2: after them
-    chalf8 wh[TAPS], wl[TAPS], nwh[DBW ? TAPS : 1], nwl[DBW ? TAPS : 1];
-    auto request = [&](int ch, chalf8 (&h)[TAPS], chalf8 (&l)[TAPS]) {
+    s3d_half8 wh[TAPS], wl[TAPS], nwh[DBW ? TAPS : 1], nwl[DBW ? TAPS : 1];
+    auto request = [&](int ch, s3d_half8 (&h)[TAPS], s3d_half8 (&l)[TAPS]) {
         const int s = ch < cu0 ? 0 : 1, c = s ? ch - cu0 : ch, cu = s ? cu1 : cu0;
         const _Float16* f0 = wimg + ((size_t)jt * KU32 + (s ? TAPS * cu0 : 0) + c) * 1024 + lane * 8;
 #pragma unroll
         for (int tap = 0; tap < TAPS; ++tap) {
-            h[tap] = *reinterpret_cast<const chalf8*>(f0 + (size_t)tap * cu * 1024);
-            l[tap] = *reinterpret_cast<const chalf8*>(f0 + (size_t)tap * cu * 1024 + 512);
+            h[tap] = *reinterpret_cast<const s3d_half8*>(f0 + (size_t)tap * cu * 1024);
+            l[tap] = *reinterpret_cast<const s3d_half8*>(f0 + (size_t)tap * cu * 1024 + 512);
         }
     };
     fetch(a.src[ch_lo < cu0 ? 0 : 1], ch_lo < cu0 ? ch_lo : ch_lo - cu0, ch_lo < cu0 ? 0 : a.src[0].C);
@@ -1176,13 +1164,13 @@ __global__ __launch_bounds__(256) void conv3x3_small_f16x3_kernel(const ConvLaun
 #pragma unroll
         for (int tap = 0; tap < TAPS; ++tap) {
             const int toff = TAPS == 9 ? (tap / 3) * Wp + tap % 3 : 0;
-            chalf8 bh[PT], bl[PT];
+            s3d_half8 bh[PT], bl[PT];
 #pragma unroll
             for (int pt = 0; pt < PT; ++pt) {
                 const int pix = pix0[pt] + toff;
                 const int po = pix * C3_PXS + C3_SWZ(pix, g);
-                bh[pt] = *reinterpret_cast<const chalf8*>(sh + po);
-                bl[pt] = *reinterpret_cast<const chalf8*>(sl + po);
+                bh[pt] = *reinterpret_cast<const s3d_half8*>(sh + po);
+                bl[pt] = *reinterpret_cast<const s3d_half8*>(sl + po);
             }
             if (!a.single_pass) {
 #pragma unroll
@@ -1722,7 +1710,7 @@ __global__ __launch_bounds__(256) void vgg_first_f16x3_kernel(const float* __res
     const int m = lane & 15, g = lane >> 4;
     const int S = a.H;
     const long hw = (long)S * S;
-    chalf8 wh[4], wl[4];
+    s3d_half8 wh[4], wl[4];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
         float v[8];
@@ -1772,15 +1760,13 @@ __global__ __launch_bounds__(256) void vgg_first_f16x3_kernel(const float* __res
 #pragma unroll
         for (int t = 0; t < 8; ++t) v[t] = ((okm >> t) & 1u) ? ((raw[t] + 1.f) / 2.f - kmu[t]) / ksd[t] : 0.f;
         if (tile + stride < n_tiles) gather(tile + stride);
-        chalf8 bh, bl;
+        s3d_half8 bh, bl;
         s3d_split8(v, bh, bl);
         S3D_SPLIT_SETTLE();   // partial-register split results feed the MFMAs below straight from registers
         f32x4 acc[1][4];
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
-            acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[nt], bl, zero4(), 0, 0, 0);
-            acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[nt], bh, acc[0][nt], 0, 0, 0);
-            acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[nt], bh, acc[0][nt], 0, 0, 0);
+            acc[0][nt] = s3d_mfma3(wh[nt], wl[nt], bh, bl, zero4());
         }
         const int tx = (int)(tile % tiles_x);
         const long r = tile / tiles_x;

@@ -300,9 +300,7 @@ __device__ __forceinline__ void slice_token_task(const SampleArgs& a, const floa
                 fh[(st + 1) & 1] = *reinterpret_cast<const s3d_half8*>(sw + (jn * 3 + kn) * 1024 + lane * 8);
                 fl[(st + 1) & 1] = *reinterpret_cast<const s3d_half8*>(sw + (jn * 3 + kn) * 1024 + 512 + lane * 8);
             }
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[st & 1], bl[kk], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fl[st & 1], bh[kk], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[st & 1], bh[kk], acc[j], 0, 0, 0);
+            acc[j] = s3d_mfma3(fh[st & 1], fl[st & 1], bh[kk], bl[kk], acc[j]);
         }
     } else {
 #pragma unroll
@@ -1351,9 +1349,7 @@ __global__ __launch_bounds__(256) void sample_tokens_gt_kernel(const SampleGtArg
                         for (int j = 0; j < 8; ++j) {
                             const s3d_half8 fh = *reinterpret_cast<const s3d_half8*>(sw + (j * 2 + kk) * 1024 + lane * 8);
                             const s3d_half8 fl = *reinterpret_cast<const s3d_half8*>(sw + (j * 2 + kk) * 1024 + 512 + lane * 8);
-                            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh, bl, acc[j], 0, 0, 0);
-                            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fl, bh, acc[j], 0, 0, 0);
-                            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh, bh, acc[j], 0, 0, 0);
+                            acc[j] = s3d_mfma3(fh, fl, bh, bl, acc[j]);
                         }
                     }
                 } else {

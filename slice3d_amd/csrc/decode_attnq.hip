@@ -59,9 +59,7 @@ __global__ __launch_bounds__(256, 2) void attn_layer_q_kernel(float* X, long gro
         const _Float16* src0 = part < 3 ? g_in + (size_t)h * AQ_WIN_HALFS + part * AQ3_SLOT_HALFS
                                         : g_out + (size_t)h * AQ_WO_HALFS;
         const int i = wave + 4 * k;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src0 + i * 512 + lane * 8),
-                                         (__attribute__((address_space(3))) void*)(s_win + buf * AQ3_SLOT_HALFS + i * 512),
-                                         16, 0, 0);
+        S3D_DMA_PIECE(src0 + i * 512 + lane * 8, s_win + buf * AQ3_SLOT_HALFS + i * 512, 0);
     };
     auto dma_phase = [&](int ph, int buf) {
 #pragma unroll
@@ -126,7 +124,7 @@ __global__ __launch_bounds__(256, 2) void attn_layer_q_kernel(float* X, long gro
         {   // hand-issued reads (a compiler-visible LDS read is guarded with vmcnt(0) against the ring's DMA in flight)
             f32x4 bo[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) AQ_READ(bo[j], lpar, (384 + 32 * (j >> 1) + 4 * (j & 1)) * 4);
+            for (int j = 0; j < 8; ++j) S3D_DS_READ(bo[j], lpar, (384 + 32 * (j >> 1) + 4 * (j & 1)) * 4);
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(bo[0]), "+v"(bo[1]), "+v"(bo[2]), "+v"(bo[3]), "+v"(bo[4]), "+v"(bo[5]), "+v"(bo[6]), "+v"(bo[7]));
 #pragma unroll
@@ -136,11 +134,11 @@ __global__ __launch_bounds__(256, 2) void attn_layer_q_kernel(float* X, long gro
         }
         // rows of the item: both halves in registers for the whole item (the high halves used to be parked in LDS and re-read
         // with every k-step: 2 of 6 fragment reads)
-        half8q xl[2][4], xh[2][4];
+        s3d_half8 xl[2][4], xh[2][4];
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
-            for (int u = 0; u < 4; ++u) split8x<BF>(xf[r][u][0], xf[r][u][1], xh[r][u], xl[r][u]);
+            for (int u = 0; u < 4; ++u) s3d_split8x<BF>(xf[r][u][0], xf[r][u][1], xh[r][u], xl[r][u]);
         const bool more_items = item + gridDim.x < items;
 #pragma unroll 1
         for (int h = 0; h < 4; ++h) {
@@ -156,8 +154,8 @@ __global__ __launch_bounds__(256, 2) void attn_layer_q_kernel(float* X, long gro
                     const unsigned lq = lpar4 + (unsigned)h * 128u, lv = lparm + (unsigned)h * 128u;
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        AQ_READ(bq[j], lq, 64 * j);
-                        AQ_READ(bk[j], lq, 512 + 64 * j);
+                        S3D_DS_READ(bq[j], lq, 64 * j);
+                        S3D_DS_READ(bk[j], lq, 512 + 64 * j);
                         AQ_READ32(bv[j], lv, 1024 + 64 * j);
                     }
                 }
@@ -167,12 +165,12 @@ __global__ __launch_bounds__(256, 2) void attn_layer_q_kernel(float* X, long gro
                 f32x4 d[2][2], c0[2];   // c0: the bias opens both row tiles' accumulations (C operand of k-step 0, no copies)
                 // fragment pairs (hi | lo) of the two 16-row tiles j and the high halves of the wave's two row tiles for
                 // k-step U, all read one k-step ahead (6 reads in flight under the 12 MFMAs of the current step)
-                half8q fh[2][2], fl[2][2];
+                s3d_half8 fh[2][2], fl[2][2];
 #define AQ_STEP_READS(B, U)                                          \
-    AQ_READ(fh[B][0], lwa, (U) * 2048);                              \
-    AQ_READ(fl[B][0], lwa, (U) * 2048 + 1024);                       \
-    AQ_READ(fh[B][1], lwa, (4 + (U)) * 2048);                        \
-    AQ_READ(fl[B][1], lwa, (4 + (U)) * 2048 + 1024);
+    S3D_DS_READ(fh[B][0], lwa, (U) * 2048);                              \
+    S3D_DS_READ(fl[B][0], lwa, (U) * 2048 + 1024);                       \
+    S3D_DS_READ(fh[B][1], lwa, (4 + (U)) * 2048);                        \
+    S3D_DS_READ(fl[B][1], lwa, (4 + (U)) * 2048 + 1024);
 #define AQ_STEP_MFMA(B, U)                                                                                   \
     _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                          \
         if (j == 1) {                                                                                        \
@@ -181,29 +179,29 @@ __global__ __launch_bounds__(256, 2) void attn_layer_q_kernel(float* X, long gro
             __builtin_amdgcn_sched_barrier(0);                                                               \
         }                                                                                                    \
         if (part < 2) { /* D^T = W X^T */                                                                    \
-            d[0][j] = mfma3q<SINGLE, BF>(fh[B][j], fl[B][j], xh[0][U], xl[0][U], (U) == 0 ? c0[j] : d[0][j]);    \
-            d[1][j] = mfma3q<SINGLE, BF>(fh[B][j], fl[B][j], xh[1][U], xl[1][U], (U) == 0 ? c0[j] : d[1][j]);    \
+            d[0][j] = s3d_mfma3<SINGLE, BF>(fh[B][j], fl[B][j], xh[0][U], xl[0][U], (U) == 0 ? c0[j] : d[0][j]);    \
+            d[1][j] = s3d_mfma3<SINGLE, BF>(fh[B][j], fl[B][j], xh[1][U], xl[1][U], (U) == 0 ? c0[j] : d[1][j]);    \
         } else { /* D = X W^T */                                                                             \
-            d[0][j] = mfma3q<SINGLE, BF>(xh[0][U], xl[0][U], fh[B][j], fl[B][j], (U) == 0 ? c0[j] : d[0][j]);    \
-            d[1][j] = mfma3q<SINGLE, BF>(xh[1][U], xl[1][U], fh[B][j], fl[B][j], (U) == 0 ? c0[j] : d[1][j]);    \
+            d[0][j] = s3d_mfma3<SINGLE, BF>(xh[0][U], xl[0][U], fh[B][j], fl[B][j], (U) == 0 ? c0[j] : d[0][j]);    \
+            d[1][j] = s3d_mfma3<SINGLE, BF>(xh[1][U], xl[1][U], fh[B][j], fl[B][j], (U) == 0 ? c0[j] : d[1][j]);    \
         }                                                                                                    \
     }                                                                                                        \
     __builtin_amdgcn_sched_barrier(0);
                 AQ_STEP_READS(0, 0)
                 AQ_STEP_READS(1, 1)
-                AQ_WAIT4(4, fh[0][0], fl[0][0], fh[0][1], fl[0][1]);
+                S3D_LGKM_WAIT4(4, fh[0][0], fl[0][0], fh[0][1], fl[0][1]);
                 if (part == 0)   // the head's bias reads are older than the fragment reads: landed with this wait
                     asm volatile("" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bk[0]), "+v"(bk[1]), "+v"(bv[0]), "+v"(bv[1]));
 #pragma unroll
                 for (int j = 0; j < 2; ++j) c0[j] = part == 0 ? bq[j] : part == 1 ? bk[j] : f32x4{bv[j], bv[j], bv[j], bv[j]};
                 AQ_STEP_MFMA(0, 0)
                 AQ_STEP_READS(0, 2)
-                AQ_WAIT4(4, fh[1][0], fl[1][0], fh[1][1], fl[1][1]);
+                S3D_LGKM_WAIT4(4, fh[1][0], fl[1][0], fh[1][1], fl[1][1]);
                 AQ_STEP_MFMA(1, 1)
                 AQ_STEP_READS(1, 3)
-                AQ_WAIT4(4, fh[0][0], fl[0][0], fh[0][1], fl[0][1]);
+                S3D_LGKM_WAIT4(4, fh[0][0], fl[0][0], fh[0][1], fl[0][1]);
                 AQ_STEP_MFMA(0, 2)
-                AQ_WAIT4(0, fh[1][0], fl[1][0], fh[1][1], fl[1][1]);
+                S3D_LGKM_WAIT4(0, fh[1][0], fl[1][0], fh[1][1], fl[1][1]);
                 AQ_STEP_MFMA(1, 3)
 #undef AQ_STEP_READS
 #undef AQ_STEP_MFMA
@@ -223,26 +221,22 @@ __global__ __launch_bounds__(256, 2) void attn_layer_q_kernel(float* X, long gro
             // are), and P V runs on v_mfma_f32_16x16x16_f16 (k-slot 4g + t <-> key 4g + t).  9 MFMAs of 4 passes per
             // query instead of 16 fp32 MFMAs of 8.  Scores in log2 units (the scale carries log2 e), softmax by v_exp_f32.
             // Both queries of the wave go through each stage together (independent chains), and every group of splits
-            // is followed by AQ_SETTLE before the MFMAs that read it: the halves are written by 16-bit partial-register
+            // is followed by S3D_SPLIT_SETTLE before the MFMAs that read it: the halves are written by 16-bit partial-register
             // asm ops (v_fma_mixlo/hi_f16) whose write -> MFMA-read spacing the compiler does not pad (one wait state
             // measured as too few on gfx950: wrong P V products in some schedules, fixed by the padding alone).
-#define AQ_SETTLE()                                 \
-    __builtin_amdgcn_sched_barrier(0);              \
-    asm volatile("s_nop 15" ::: "memory");          \
-    __builtin_amdgcn_sched_barrier(0);
-            half8q oh[2], ol[2];
+            s3d_half8 oh[2], ol[2];
             {
-                half8q kh[2], kl[2], qh[2], ql[2];
+                s3d_half8 kh[2], kl[2], qh[2], ql[2];
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
-                    split8x<BF>(kd[r][0], kd[r][1], kh[r], kl[r]);
-                    split8x<BF>(qd[r][0] * scale, qd[r][1] * scale, qh[r], ql[r]);
+                    s3d_split8x<BF>(kd[r][0], kd[r][1], kh[r], kl[r]);
+                    s3d_split8x<BF>(qd[r][0] * scale, qd[r][1] * scale, qh[r], ql[r]);
                 }
-                AQ_SETTLE()
+                S3D_SPLIT_SETTLE()
                 f32x4 s[2];
 #pragma unroll
-                for (int r = 0; r < 2; ++r) s[r] = mfma3q<SINGLE, BF>(kh[r], kl[r], qh[r], ql[r], zero4());
-                half4q ph[2], pl[2], vh[2][2], vl[2][2];
+                for (int r = 0; r < 2; ++r) s[r] = s3d_mfma3<SINGLE, BF>(kh[r], kl[r], qh[r], ql[r], zero4());
+                s3d_half4 ph[2], pl[2], vh[2][2], vl[2][2];
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
                     float e[4];
@@ -252,14 +246,14 @@ __global__ __launch_bounds__(256, 2) void attn_layer_q_kernel(float* X, long gro
                         e[i] = (4 * g + i < T) ? s[r][i] : -1e30f;
                         mx = fmaxf(mx, e[i]);
                     }
-                    mx = colmax16(mx);
+                    mx = s3d_colmax16(mx);
                     float den = 0.f;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         e[i] = __builtin_amdgcn_exp2f(e[i] - mx);   // masked keys: exp2(-1e30) = 0
                         den += e[i];
                     }
-                    const float inv = __builtin_amdgcn_rcpf(colsum16(den));   // v_rcp_f32, 1 ulp
+                    const float inv = __builtin_amdgcn_rcpf(s3d_colsum16(den));   // v_rcp_f32, 1 ulp
                     f32x4 pr = f32x4{e[0] * inv, e[1] * inv, e[2] * inv, e[3] * inv};
                     if (TRAIN && ta.d0.p > 0.f) {   // lane (query token m, g): keys 4g .. 4g+3 of probability row (row, head)
                         float mk[4];
@@ -269,18 +263,18 @@ __global__ __launch_bounds__(256, 2) void attn_layer_q_kernel(float* X, long gro
                         s3d_drop4(ta.d0, (rowq * 4 + (unsigned)h) * 16 + 4 * go, mk);
                         pr = f32x4{pr[0] * mk[0], pr[1] * mk[1], pr[2] * mk[2], pr[3] * mk[3]};
                     }
-                    split4x<BF>(pr, ph[r], pl[r]);
+                    s3d_split4x<BF>(pr, ph[r], pl[r]);
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) split4x<BF>(vd[r][j], vh[r][j], vl[r][j]);
+                    for (int j = 0; j < 2; ++j) s3d_split4x<BF>(vd[r][j], vh[r][j], vl[r][j]);
                 }
-                AQ_SETTLE()
+                S3D_SPLIT_SETTLE()
                 f32x4 od[2][2];
 #pragma unroll
                 for (int r = 0; r < 2; ++r)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) od[r][j] = mfma3h<SINGLE, BF>(vh[r][j], vl[r][j], ph[r], pl[r], zero4());
+                    for (int j = 0; j < 2; ++j) od[r][j] = s3d_mfma3_k16<SINGLE, BF>(vh[r][j], vl[r][j], ph[r], pl[r], zero4());
 #pragma unroll
-                for (int r = 0; r < 2; ++r) split8x<BF>(od[r][0], od[r][1], oh[r], ol[r]);
+                for (int r = 0; r < 2; ++r) s3d_split8x<BF>(od[r][0], od[r][1], oh[r], ol[r]);
                 if (TRAIN) {   // O rows of this head: tiles j = 0, 1 are dims 4g + i and 16 + 4g + i of token m = one 128-byte
                                // line per token after the lane exchange (s3d_full_line_pair)
                     int mo = m, go = g;
@@ -295,19 +289,18 @@ __global__ __launch_bounds__(256, 2) void attn_layer_q_kernel(float* X, long gro
                     }
                 }
             }
-#undef AQ_SETTLE
             ring_barrier(h, 3);   // out_proj fragments have landed; the v slot is free
             // the next phase is the next head's q, or phase 0 of the next item (issued even after the last item: no
             // branch in the MFMA stream; the kernel drains vmcnt before it ends)
             const int oph = (4 * h + 3 + 3) & 15, obuf = (int)((ps + 3) & 3);
             {
                 const unsigned lwa = lds_ring + (unsigned)(ps & 3) * (AQ3_SLOT_HALFS * 2);
-                half8q wh[2][2], wl[2][2];   // [buffer][tile of the pair]
+                s3d_half8 wh[2][2], wl[2][2];   // [buffer][tile of the pair]
 #define AQ_O_READS(B, G)                                             \
-    AQ_READ(wh[B][0], lwa, (2 * (G)) * 2048);                        \
-    AQ_READ(wl[B][0], lwa, (2 * (G)) * 2048 + 1024);                 \
-    AQ_READ(wh[B][1], lwa, (2 * (G) + 1) * 2048);                    \
-    AQ_READ(wl[B][1], lwa, (2 * (G) + 1) * 2048 + 1024);
+    S3D_DS_READ(wh[B][0], lwa, (2 * (G)) * 2048);                        \
+    S3D_DS_READ(wl[B][0], lwa, (2 * (G)) * 2048 + 1024);                 \
+    S3D_DS_READ(wh[B][1], lwa, (2 * (G) + 1) * 2048);                    \
+    S3D_DS_READ(wl[B][1], lwa, (2 * (G) + 1) * 2048 + 1024);
 #define AQ_O_MFMA(B, G)                                                                                      \
     _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                          \
         if (q == 1) {                                                                                        \
@@ -316,20 +309,20 @@ __global__ __launch_bounds__(256, 2) void attn_layer_q_kernel(float* X, long gro
             __builtin_amdgcn_sched_barrier(0);                                                               \
         }                                                                                                    \
         _Pragma("unroll") for (int r = 0; r < 2; ++r)                                                        \
-            acc_o[r][2 * (G) + q] = mfma3q<SINGLE, BF>(wh[B][q], wl[B][q], oh[r], ol[r], acc_o[r][2 * (G) + q]); \
+            acc_o[r][2 * (G) + q] = s3d_mfma3<SINGLE, BF>(wh[B][q], wl[B][q], oh[r], ol[r], acc_o[r][2 * (G) + q]); \
     }                                                                                                        \
     __builtin_amdgcn_sched_barrier(0);
                 AQ_O_READS(0, 0)
                 AQ_O_READS(1, 1)
-                AQ_WAIT4(4, wh[0][0], wl[0][0], wh[0][1], wl[0][1]);
+                S3D_LGKM_WAIT4(4, wh[0][0], wl[0][0], wh[0][1], wl[0][1]);
                 AQ_O_MFMA(0, 0)
                 AQ_O_READS(0, 2)
-                AQ_WAIT4(4, wh[1][0], wl[1][0], wh[1][1], wl[1][1]);
+                S3D_LGKM_WAIT4(4, wh[1][0], wl[1][0], wh[1][1], wl[1][1]);
                 AQ_O_MFMA(1, 1)
                 AQ_O_READS(1, 3)
-                AQ_WAIT4(4, wh[0][0], wl[0][0], wh[0][1], wl[0][1]);
+                S3D_LGKM_WAIT4(4, wh[0][0], wl[0][0], wh[0][1], wl[0][1]);
                 AQ_O_MFMA(0, 2)
-                AQ_WAIT4(0, wh[1][0], wl[1][0], wh[1][1], wl[1][1]);
+                S3D_LGKM_WAIT4(0, wh[1][0], wl[1][0], wh[1][1], wl[1][1]);
                 AQ_O_MFMA(1, 3)
 #undef AQ_O_READS
 #undef AQ_O_MFMA
@@ -383,22 +376,22 @@ __global__ __launch_bounds__(256, 2) void attn_layer_q_kernel(float* X, long gro
         f32x4 ga[8], be[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            AQ_READ(ga[j], lpar, (512 + 32 * (j >> 1) + 4 * (j & 1)) * 4);
-            AQ_READ(be[j], lpar, (640 + 32 * (j >> 1) + 4 * (j & 1)) * 4);
+            S3D_DS_READ(ga[j], lpar, (512 + 32 * (j >> 1) + 4 * (j & 1)) * 4);
+            S3D_DS_READ(be[j], lpar, (640 + 32 * (j >> 1) + 4 * (j & 1)) * 4);
         }
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             f32x4 s4 = acc_o[r][0];
 #pragma unroll
             for (int j = 1; j < 8; ++j) s4 += acc_o[r][j];
-            const float mean = colsum16((s4[0] + s4[1]) + (s4[2] + s4[3])) * (1.f / 128.f);
+            const float mean = s3d_colsum16((s4[0] + s4[1]) + (s4[2] + s4[3])) * (1.f / 128.f);
             f32x4 v4 = zero4();
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 acc_o[r][j] -= mean;
                 v4 += acc_o[r][j] * acc_o[r][j];
             }
-            const float rstd = __builtin_amdgcn_rsqf(colsum16((v4[0] + v4[1]) + (v4[2] + v4[3])) * (1.f / 128.f) + 1e-5f);
+            const float rstd = __builtin_amdgcn_rsqf(s3d_colsum16((v4[0] + v4[1]) + (v4[2] + v4[3])) * (1.f / 128.f) + 1e-5f);
             if (r == 0)
                 asm volatile("s_waitcnt lgkmcnt(0)"
                              : "+v"(ga[0]), "+v"(ga[1]), "+v"(ga[2]), "+v"(ga[3]), "+v"(ga[4]), "+v"(ga[5]), "+v"(ga[6]), "+v"(ga[7]),
@@ -490,7 +483,7 @@ __global__ void pack_attn_q_f16x3_kernel(const float* __restrict__ win, const fl
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             if (bf16) {   // bf16 bit patterns (S3D_PREC_BF16), no low halves
-                dst[t] = __builtin_bit_cast(_Float16, (unsigned short)(bf16_pair_q(v[t], 0.f) & 0xFFFFu));
+                dst[t] = __builtin_bit_cast(_Float16, (unsigned short)(s3d_bf16_pair(v[t], 0.f) & 0xFFFFu));
                 dst[512 + t] = (_Float16)0.f;
                 continue;
             }

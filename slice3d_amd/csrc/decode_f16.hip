@@ -1,7 +1,7 @@
 // decode_f16.hip — split-precision ("f16x3") variant of the decoder FFN kernel.
 //
 // Every fp32 operand x is split as x = hi + lo with hi = f16(x), lo = f16(x - hi)  (22 significant bits),
-// and each product is evaluated as hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 with fp32
+// and each product is evaluated as three f16 products (s3d_mfma3, f16x3.h) on v_mfma_f32_16x16x32_f16 with fp32
 // accumulation: products of two f16 values are exact in fp32, the dropped lo*lo term is < 2^-22 relative,
 // so the result is fp32-class (measured against the fp32 path in tests) at 3 MFMAs of 16 cycles per
 // 16x16x32 block instead of 8 MFMAs of 32 cycles — 5.3x fewer matrix-pipe cycles than the f32 kernel.
@@ -15,9 +15,8 @@
 
 #include "decode.h"
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split8(const float (&x)[8], half8& hi, half8& lo) {
+// scalar convert - subtract - convert split of the rows (the same values as s3d_split8, a different instruction sequence)
+__device__ __forceinline__ void split8(const float (&x)[8], s3d_half8& hi, s3d_half8& lo) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
         const _Float16 h = (_Float16)x[t];
@@ -25,51 +24,21 @@ __device__ __forceinline__ void split8(const float (&x)[8], half8& hi, half8& lo
         lo[t] = (_Float16)(x[t] - (float)h);
     }
 }
-__device__ __forceinline__ f32x4 mfma3(const half8 ah, const half8 al, const half8 bh, const half8 bl, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
-    return c;
-}
-__device__ __forceinline__ half8 ldh8(const _Float16* p) { return *reinterpret_cast<const half8*>(p); }
 // ---------------------------------------------------------------------------------------------
 // BF (S3D_PREC_BF16, round 5): the single-pass mode on the bf16 MFMA — what BASELINE configs[1] literally names.  The 16-bit
-// lanes of the operand containers (half8 / half2v) then hold bf16 bit patterns: weights from the bf16 image
+// lanes of the operand containers (s3d_half8 / s3d_half2) then hold bf16 bit patterns: weights from the bf16 image
 // (launch_pack_ffn_f16x3(..., bf16 = 1)), activations rounded by v_cvt_pk_bf16_f32.  Same rate as the f16 instruction, 8
 // significand bits instead of 11: a throughput mode further from fp32 than S3D_PREC_F16, never the headline.
 // ---------------------------------------------------------------------------------------------
-typedef __bf16 bf8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-template <bool BF>
-__device__ __forceinline__ f32x4 mfma_hh(const half8 a, const half8 b, const f32x4 c) {
-    if (BF) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8_t, a), __builtin_bit_cast(bf8_t, b), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned bf16_pair(float a, float b) {   // bf16(a) | bf16(b) << 16, round to nearest even
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, bf2_t));
-}
-__device__ __forceinline__ float bf16_lane(const half8 v, int t) {   // the fp32 value of bf16 lane t
+__device__ __forceinline__ float bf16_lane(const s3d_half8 v, int t) {   // the fp32 value of bf16 lane t
     return __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, v[t]) << 16);
 }
 // rows in BF mode: hi = bf16(x) (the MFMA operand), lo = f16(x - hi) (only the epilogue's residual reads it)
-__device__ __forceinline__ void split8_bf(const float (&x)[8], half8& hi, half8& lo) {
-    typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-    const u4_t h = {bf16_pair(x[0], x[1]), bf16_pair(x[2], x[3]), bf16_pair(x[4], x[5]), bf16_pair(x[6], x[7])};
-    hi = __builtin_bit_cast(half8, h);
+__device__ __forceinline__ void split8_bf(const float (&x)[8], s3d_half8& hi, s3d_half8& lo) {
+    const s3d_uint4 h = {s3d_bf16_pair(x[0], x[1]), s3d_bf16_pair(x[2], x[3]), s3d_bf16_pair(x[4], x[5]), s3d_bf16_pair(x[6], x[7])};
+    hi = __builtin_bit_cast(s3d_half8, h);
 #pragma unroll
     for (int t = 0; t < 8; ++t) lo[t] = (_Float16)(x[t] - bf16_lane(hi, t));
-}
-// global -> LDS copy of one 32 KiB weight chunk by LDS-DMA (1 KiB per wave-instruction, no VGPR staging)
-__device__ __forceinline__ void dma_chunk32k(const _Float16* gsrc, _Float16* ldst, int wave, int lane, int nwaves) {
-    for (int piece = wave; piece < 32; piece += nwaves)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gsrc + piece * 512 + lane * 8),
-                                         (__attribute__((address_space(3))) void*)(ldst + piece * 512), 16, 0, 0);
-}
-__device__ __forceinline__ float quad_sum16(float v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
 }
 
 #define F16_CHUNK_HALFS 16384   // 32 KiB: W1 hi | W1 lo | W2 hi | W2 lo, 4096 halfs each
@@ -102,8 +71,6 @@ __device__ __forceinline__ float quad_sum16(float v) {
 #ifndef PIPE_R
 #define PIPE_R 2     // 16-row tiles per wave: 2 = two workgroups per CU (256 VGPRs), 4 = one (512 VGPRs, half the LDS / L2 traffic)
 #endif
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float float2v __attribute__((ext_vector_type(2)));
 #define SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 #define SG_MFMA 0x008
 #define SG_VALU 0x002
@@ -116,26 +83,20 @@ typedef float float2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void dma_pieces(const _Float16* gchunk, _Float16* lbuf, int p0, int p1, int wave, int lane) {
     constexpr int PER = 16 / PIPE_WAVES;
     const int first = p0 + wave * PER;
-    const __attribute__((address_space(1))) void* g = (const __attribute__((address_space(1))) void*)(gchunk + first * 512 + lane * 8);
-    __attribute__((address_space(3))) void* l = (__attribute__((address_space(3))) void*)(lbuf + first * 512);
-    __builtin_amdgcn_global_load_lds(g, l, 16, 0, 0);
-    if (PER > 1) __builtin_amdgcn_global_load_lds(g, l, 16, 1024, 0);
-    if (PER > 2) __builtin_amdgcn_global_load_lds(g, l, 16, 2048, 0);
-    if (PER > 3) __builtin_amdgcn_global_load_lds(g, l, 16, 3072, 0);
+    s3d_dma_pieces<PER>(gchunk + first * 512 + lane * 8, lbuf + first * 512);
 }
-__device__ __forceinline__ half8 cat4(half2v a, half2v b, half2v c, half2v d) {
-    typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-    const half4v ab = __builtin_shufflevector(a, b, 0, 1, 2, 3), cd = __builtin_shufflevector(c, d, 0, 1, 2, 3);
+__device__ __forceinline__ s3d_half8 cat4(s3d_half2 a, s3d_half2 b, s3d_half2 c, s3d_half2 d) {
+    const s3d_half4 ab = __builtin_shufflevector(a, b, 0, 1, 2, 3), cd = __builtin_shufflevector(c, d, 0, 1, 2, 3);
     return __builtin_shufflevector(ab, cd, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 // hi/lo halves of four values, 1.5 VALU per value (s3d_split2: v_cvt_pk_f16_f32 + v_fma_mix{lo,hi}_f16, bit-identical to
 // convert - subtract - convert).  The partial-register results feed MFMAs a whole phase later: no settle needed here.
-__device__ __forceinline__ void split4_pk(float a0, float a1, float a2, float a3, half2v& h0, half2v& h1, half2v& l0, half2v& l1) {
+__device__ __forceinline__ void split4_pk(float a0, float a1, float a2, float a3, s3d_half2& h0, s3d_half2& h1, s3d_half2& l0, s3d_half2& l1) {
     unsigned uh0, ul0, uh1, ul1;
     s3d_split2(a0, a1, uh0, ul0);
     s3d_split2(a2, a3, uh1, ul1);
-    h0 = __builtin_bit_cast(half2v, uh0); l0 = __builtin_bit_cast(half2v, ul0);
-    h1 = __builtin_bit_cast(half2v, uh1); l1 = __builtin_bit_cast(half2v, ul1);
+    h0 = __builtin_bit_cast(s3d_half2, uh0); l0 = __builtin_bit_cast(s3d_half2, ul0);
+    h1 = __builtin_bit_cast(s3d_half2, uh1); l1 = __builtin_bit_cast(s3d_half2, ul1);
 }
 // relu as ONE v_max_f32: fmaxf on an MFMA result costs a canonicalising v_max first, and hipcc folds
 // __builtin_amdgcn_fmed3f(v, 0, inf) back into that pair (seen in the ISA: 8 v_max per D tile)
@@ -146,11 +107,11 @@ __device__ __forceinline__ float relu1(float v) {
 }
 // relu + split of the 4 pre-activations of one D tile: hi = f16(max(v,0)), lo = f16(max(v,0) - hi)
 template <bool SINGLE, bool BF = false>
-__device__ __forceinline__ void relu_split4(const f32x4 v, half2v& h0, half2v& h1, half2v& l0, half2v& l1) {
+__device__ __forceinline__ void relu_split4(const f32x4 v, s3d_half2& h0, s3d_half2& h1, s3d_half2& l0, s3d_half2& l1) {
     if (BF) {   // bf16 halves of relu(v); the low halves are not used by the single-pass product
         const float inf = __builtin_inff();
-        h0 = __builtin_bit_cast(half2v, bf16_pair(__builtin_amdgcn_fmed3f(v[0], 0.f, inf), __builtin_amdgcn_fmed3f(v[1], 0.f, inf)));
-        h1 = __builtin_bit_cast(half2v, bf16_pair(__builtin_amdgcn_fmed3f(v[2], 0.f, inf), __builtin_amdgcn_fmed3f(v[3], 0.f, inf)));
+        h0 = __builtin_bit_cast(s3d_half2, s3d_bf16_pair(__builtin_amdgcn_fmed3f(v[0], 0.f, inf), __builtin_amdgcn_fmed3f(v[1], 0.f, inf)));
+        h1 = __builtin_bit_cast(s3d_half2, s3d_bf16_pair(__builtin_amdgcn_fmed3f(v[2], 0.f, inf), __builtin_amdgcn_fmed3f(v[3], 0.f, inf)));
         l0 = h0; l1 = h1;
         return;
     }
@@ -202,7 +163,7 @@ __device__ __forceinline__ void ffn_draw(FfnActState& as, int c, int a2, int r2)
 }
 // D tile (a2, r2) of chunk c: pre-activation -> f16 hi/lo halves of GEMM2's B operand
 template <int MODE, bool SINGLE, bool BF = false>
-__device__ __forceinline__ void ffn_act4(const f32x4 v, half2v& h0, half2v& h1, half2v& l0, half2v& l1, FfnActState& as,
+__device__ __forceinline__ void ffn_act4(const f32x4 v, s3d_half2& h0, s3d_half2& h1, s3d_half2& l0, s3d_half2& l1, FfnActState& as,
                                          const FfnTrainArgs& ta, const FfnBwdArgs& ba, int c, int a2, int r2) {
     if (MODE == 2 || MODE == 3) {
         float a[4] = {relu1(v[0]), relu1(v[1]), relu1(v[2]), relu1(v[3])};
@@ -244,40 +205,28 @@ __device__ __forceinline__ void ffn_act4(const f32x4 v, half2v& h0, half2v& h1, 
     }
 }
 
-// LDS fragment reads and their waits are issued by hand.  hipcc models a pending LDS-DMA as an LDS access of unknown
-// order: while the refill of the other buffer is in flight it either degrades every LDS wait to lgkmcnt(0) (waiting
-// for the reads it has just issued for the NEXT group) or guards each read with vmcnt(0) (waiting for the refill) —
-// measured in the ISA of three variants of this loop.  An asm read is invisible to that bookkeeping; DS_WAIT names the
-// registers it releases, so their consumers cannot be scheduled above it.  LDS returns in order: lgkmcnt(2) leaves
-// exactly the two reads of the next group outstanding.
-#define DS_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-#define DS_WAIT2(n, r0, r1) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(r0), "+v"(r1) : "n"(n))
-#define DS_WAIT4(n, r0, r1, r2, r3) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) : "n"(n))
-#define DS_WAIT1(n, r0) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(r0) : "n"(n))
-#define DS_WAIT3(n, r0, r1, r2) asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(r0), "+v"(r1), "+v"(r2) : "n"(n))
-#define DS_WAIT5(n, r0, r1, r2, r3, r4) \
-    asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4) : "n"(n))
-
+// LDS fragment reads and their waits are issued by hand (S3D_DS_READ / S3D_LGKM_WAIT*, f16x3.h; hipcc's own waits were
+// measured in the ISA of three variants of this loop).  lgkmcnt(2) leaves exactly the two reads of the next group outstanding.
 // phase A group K = (u, a): reads of group K+1 (or of phase B's first tile), 6 MFMAs, VALU slice on even K
 #define FFN_GROUP_A(K)                                                                                               \
     {                                                                                                                \
         constexpr int u = (K) >> 1, a = (K) & 1, s = (K) & 1;                                                        \
         if (!LAST) {                                                                                                 \
             if ((K) < 7) {                                                                                           \
-                DS_READ(fh[s ^ 1], lw, ((((K) + 1) & 1) * 4 + (((K) + 1) >> 1)) * 1024);                             \
-                DS_READ(fl[s ^ 1], lw, ((((K) + 1) & 1) * 4 + (((K) + 1) >> 1)) * 1024 + 8192);                      \
+                S3D_DS_READ(fh[s ^ 1], lw, ((((K) + 1) & 1) * 4 + (((K) + 1) >> 1)) * 1024);                         \
+                S3D_DS_READ(fl[s ^ 1], lw, ((((K) + 1) & 1) * 4 + (((K) + 1) >> 1)) * 1024 + 8192);                  \
             } else {                                                                                                 \
-                DS_READ(vh[0], lw, 16384);                                                                           \
-                DS_READ(vl[0], lw, 24576);                                                                           \
+                S3D_DS_READ(vh[0], lw, 16384);                                                                       \
+                S3D_DS_READ(vl[0], lw, 24576);                                                                       \
             }                                                                                                        \
             if ((K) == 0 && MODE == 4) {                                                                             \
-                DS_WAIT2(2, fh[0], fl[0]);                                                                           \
+                S3D_LGKM_WAIT2(2, fh[0], fl[0]);                                                                     \
                 _Pragma("unroll") for (int r = 0; r < PIPE_R; ++r) { hn[0][r] = zero4(); hn[1][r] = zero4(); }        \
             } else if ((K) == 0) {                                                                                   \
-                DS_WAIT4(2, bq[0], bq[1], fh[0], fl[0]);                                                             \
+                S3D_LGKM_WAIT4(2, bq[0], bq[1], fh[0], fl[0]);                                                       \
                 _Pragma("unroll") for (int r = 0; r < PIPE_R; ++r) { hn[0][r] = bq[0]; hn[1][r] = bq[1]; }            \
             } else {                                                                                                 \
-                DS_WAIT2(2, fh[s], fl[s]);                                                                           \
+                S3D_LGKM_WAIT2(2, fh[s], fl[s]);                                                                     \
             }                                                                                                        \
             if (!SINGLE) {                                                                                           \
                 _Pragma("unroll") for (int r = 0; r < PIPE_R; ++r)                                                    \
@@ -286,10 +235,10 @@ __device__ __forceinline__ void ffn_act4(const f32x4 v, half2v& h0, half2v& h1, 
                     hn[a][r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fl[s], xh[r][u], hn[a][r], 0, 0, 0);           \
             }                                                                                                        \
             _Pragma("unroll") for (int r = 0; r < PIPE_R; ++r)                                                        \
-                hn[a][r] = mfma_hh<BF>(fh[s], xh[r][u], hn[a][r]);                                                   \
+                hn[a][r] = s3d_mfma_hh<BF>(fh[s], xh[r][u], hn[a][r]);                                               \
         } else if ((K) == 7) {                                                                                       \
-            DS_READ(vh[0], lw, 16384);                                                                               \
-            DS_READ(vl[0], lw, 24576);                                                                               \
+            S3D_DS_READ(vh[0], lw, 16384);                                                                           \
+            S3D_DS_READ(vl[0], lw, 24576);                                                                           \
         }                                                                                                            \
         if ((K) % (4 / PIPE_R) == 0) {   /* 2 * PIPE_R D tiles over the 8 groups */                                   \
             constexpr int tile = (K) / (4 / PIPE_R), a2 = tile / PIPE_R, r2 = tile % PIPE_R;                         \
@@ -316,11 +265,11 @@ __device__ __forceinline__ void ffn_act4(const f32x4 v, half2v& h0, half2v& h1, 
     {                                                                                                                \
         constexpr int s = (J) & 1;                                                                                   \
         if ((J) < 7) {                                                                                               \
-            DS_READ(vh[s ^ 1], lw, 16384 + ((J) + 1) * 1024);                                                        \
-            DS_READ(vl[s ^ 1], lw, 24576 + ((J) + 1) * 1024);                                                        \
-            DS_WAIT2(2, vh[s], vl[s]);                                                                               \
+            S3D_DS_READ(vh[s ^ 1], lw, 16384 + ((J) + 1) * 1024);                                                    \
+            S3D_DS_READ(vl[s ^ 1], lw, 24576 + ((J) + 1) * 1024);                                                    \
+            S3D_LGKM_WAIT2(2, vh[s], vl[s]);                                                                         \
         } else {                                                                                                     \
-            DS_WAIT2(0, vh[s], vl[s]);                                                                               \
+            S3D_LGKM_WAIT2(0, vh[s], vl[s]);                                                                         \
         }                                                                                                            \
         if (!SINGLE) {                                                                                               \
             _Pragma("unroll") for (int r = 0; r < PIPE_R; ++r)                                                        \
@@ -329,7 +278,7 @@ __device__ __forceinline__ void ffn_act4(const f32x4 v, half2v& h0, half2v& h1, 
                 acc[r][J] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl[s], hh[r], acc[r][J], 0, 0, 0);                \
         }                                                                                                            \
         _Pragma("unroll") for (int r = 0; r < PIPE_R; ++r)                                                            \
-            acc[r][J] = mfma_hh<BF>(vh[s], hh[r], acc[r][J]);                                                        \
+            acc[r][J] = s3d_mfma_hh<BF>(vh[s], hh[r], acc[r][J]);                                                    \
         SB();                                                                                                        \
     }
 
@@ -338,26 +287,26 @@ __device__ __forceinline__ void ffn_act4(const f32x4 v, half2v& h0, half2v& h1, 
 // written here IS the issue order.  lw = LDS byte address of this lane's fragment slot in the current weight buffer,
 // lb = of its bias quad of the NEXT chunk.
 template <int MODE, bool LAST, bool SINGLE, bool BF = false>
-__device__ __forceinline__ void ffn_pipe_iter(const unsigned lw, const unsigned lb, const half8 (&xh)[PIPE_R][4],
-                                              const half8 (&xl)[PIPE_R][4], f32x4 (&acc)[PIPE_R][8],
+__device__ __forceinline__ void ffn_pipe_iter(const unsigned lw, const unsigned lb, const s3d_half8 (&xh)[PIPE_R][4],
+                                              const s3d_half8 (&xl)[PIPE_R][4], f32x4 (&acc)[PIPE_R][8],
                                               const f32x4 (&hd)[2][PIPE_R], f32x4 (&hn)[2][PIPE_R], FfnActState& as,
                                               const FfnTrainArgs& ta, const FfnBwdArgs& ba, const int c) {
-    half2v hh2[PIPE_R][4], hl2[PIPE_R][4];
-    half8 fh[2], fl[2], vh[2], vl[2];
+    s3d_half2 hh2[PIPE_R][4], hl2[PIPE_R][4];
+    s3d_half8 fh[2], fl[2], vh[2], vl[2];
     f32x4 bq[2];
     if (!LAST) {
         if (MODE != 4) {
-            DS_READ(bq[0], lb, 0);
-            DS_READ(bq[1], lb, 64);
+            S3D_DS_READ(bq[0], lb, 0);
+            S3D_DS_READ(bq[1], lb, 64);
         }
-        DS_READ(fh[0], lw, 0);
-        DS_READ(fl[0], lw, 8192);
+        S3D_DS_READ(fh[0], lw, 0);
+        S3D_DS_READ(fl[0], lw, 8192);
     }
     SB();
     // ---- phase A: hn = W1(c+1) x^T + b1(c+1)   beside   relu / split of hd (chunk c)
     FFN_GROUP_A(0) FFN_GROUP_A(1) FFN_GROUP_A(2) FFN_GROUP_A(3) FFN_GROUP_A(4) FFN_GROUP_A(5) FFN_GROUP_A(6) FFN_GROUP_A(7)
     // ---- phase B: acc += W2(c) h(c)
-    half8 hh[PIPE_R], hl[PIPE_R];
+    s3d_half8 hh[PIPE_R], hl[PIPE_R];
 #pragma unroll
     for (int r = 0; r < PIPE_R; ++r) {
         hh[r] = cat4(hh2[r][0], hh2[r][1], hh2[r][2], hh2[r][3]);
@@ -397,7 +346,7 @@ __global__ __launch_bounds__(PIPE_THREADS, (PIPE_R == 2 && PIPE_WAVES == 4) ? 2 
     if (MODE != 4)
         for (int i = threadIdx.x; i < S3D_FFN / 4; i += PIPE_THREADS) st4(s_b1 + 4 * i, ld4(w.b1 + 4 * i));
 
-    half8 xh[PIPE_R][4], xl[PIPE_R][4];
+    s3d_half8 xh[PIPE_R][4], xl[PIPE_R][4];
     f32x4 acc[PIPE_R][8];
     FfnActState as;
 #pragma unroll
@@ -416,7 +365,7 @@ __global__ __launch_bounds__(PIPE_THREADS, (PIPE_R == 2 && PIPE_WAVES == 4) ? 2 
                 const f32x4 a = ld4(p + 32 * u), b = ld4(p + 32 * u + 4);
                 sacc += ((a[0] + a[1]) + (a[2] + a[3])) + ((b[0] + b[1]) + (b[2] + b[3]));
             }
-            lmean = quad_sum16(sacc) * (1.f / 128.f);
+            lmean = quad_sum(sacc) * (1.f / 128.f);
             float vacc = 0.f;
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -424,7 +373,7 @@ __global__ __launch_bounds__(PIPE_THREADS, (PIPE_R == 2 && PIPE_WAVES == 4) ? 2 
 #pragma unroll
                 for (int t = 0; t < 4; ++t) vacc += (a[t] - lmean) * (a[t] - lmean) + (b[t] - lmean) * (b[t] - lmean);
             }
-            lrstd = 1.f / sqrtf(quad_sum16(vacc) * (1.f / 128.f) + 1e-5f);
+            lrstd = 1.f / sqrtf(quad_sum(vacc) * (1.f / 128.f) + 1e-5f);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -484,16 +433,16 @@ __global__ __launch_bounds__(PIPE_THREADS, (PIPE_R == 2 && PIPE_WAVES == 4) ? 2 
         for (int u = 0; u < 4; ++u)
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
-                const half8 fh = ldh8(sw + ((a * 4 + u) * 64 + lane) * 8);
+                const s3d_half8 fh = s3d_ldh8(sw + ((a * 4 + u) * 64 + lane) * 8);
                 if (!SINGLE) {
-                    const half8 fl = ldh8(sw + 4096 + ((a * 4 + u) * 64 + lane) * 8);
+                    const s3d_half8 fl = s3d_ldh8(sw + 4096 + ((a * 4 + u) * 64 + lane) * 8);
 #pragma unroll
                     for (int r = 0; r < PIPE_R; ++r) hdA[a][r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh, xl[r][u], hdA[a][r], 0, 0, 0);
 #pragma unroll
                     for (int r = 0; r < PIPE_R; ++r) hdA[a][r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fl, xh[r][u], hdA[a][r], 0, 0, 0);
                 }
 #pragma unroll
-                for (int r = 0; r < PIPE_R; ++r) hdA[a][r] = mfma_hh<BF>(fh, xh[r][u], hdA[a][r]);
+                for (int r = 0; r < PIPE_R; ++r) hdA[a][r] = s3d_mfma_hh<BF>(fh, xh[r][u], hdA[a][r]);
             }
     }
     __syncthreads();   // every wave is done with buffer 1 before the first refill overwrites it
@@ -555,15 +504,15 @@ __global__ __launch_bounds__(PIPE_THREADS, (PIPE_R == 2 && PIPE_WAVES == 4) ? 2 
             const long blk = row0 >> 5;
             _Float16* rb = imgr + blk * FWR_BLK_HALFS;
             _Float16* db = imgd + blk * FWR_BLK_HALFS;
-            const half8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-            half8 sel[2];   // B operand that picks channels 16c .. 16c+15 of a 32-channel k-step: B[k = 8g + t][n] = (k == 16c + n)
+            const s3d_half8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
+            s3d_half8 sel[2];   // B operand that picks channels 16c .. 16c+15 of a 32-channel k-step: B[k = 8g + t][n] = (k == 16c + n)
 #pragma unroll
             for (int c2 = 0; c2 < 2; ++c2)
 #pragma unroll
                 for (int t = 0; t < 8; ++t) sel[c2][t] = (8 * g + t == 16 * c2 + m) ? (_Float16)1.f : (_Float16)0.f;
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                half8 ah[PIPE_R], al[PIPE_R];
+                s3d_half8 ah[PIPE_R], al[PIPE_R];
 #pragma unroll
                 for (int r = 0; r < PIPE_R; ++r) {   // rows past the end are zero in both images
                     const bool ok = row0 + r * 16 + m < rows;
@@ -571,8 +520,8 @@ __global__ __launch_bounds__(PIPE_THREADS, (PIPE_R == 2 && PIPE_WAVES == 4) ? 2 
                     al[r] = ok ? xl[r][u] : z8;
                     // R image: the fragment as it is — chunk 4u + g of row 16r + m, swizzled by the row
                     const int o = (16 * r + m) * 128 + (((4 * u + g) ^ m) << 3);
-                    *reinterpret_cast<half8*>(rb + o) = ah[r];
-                    *reinterpret_cast<half8*>(rb + 4096 + o) = al[r];
+                    *reinterpret_cast<s3d_half8*>(rb + o) = ah[r];
+                    *reinterpret_cast<s3d_half8*>(rb + 4096 + o) = al[r];
                 }
                 // D^T image: x tile (A: row m, k-slot = channel) times the selector -> D layout lane (channel n, g) x rows 4g + i:
                 // the slot order of the image (tile 0 rows | tile 1 rows); products with 1.0 are exact
@@ -583,7 +532,7 @@ __global__ __launch_bounds__(PIPE_THREADS, (PIPE_R == 2 && PIPE_WAVES == 4) ? 2 
                     const f32x4 h1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[1], sel[c2], zero4(), 0, 0, 0);
                     const f32x4 l0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[0], sel[c2], zero4(), 0, 0, 0);
                     const f32x4 l1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[1], sel[c2], zero4(), 0, 0, 0);
-                    half8 oh, ol;
+                    s3d_half8 oh, ol;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         oh[i] = (_Float16)h0[i]; oh[4 + i] = (_Float16)h1[i];
@@ -591,8 +540,8 @@ __global__ __launch_bounds__(PIPE_THREADS, (PIPE_R == 2 && PIPE_WAVES == 4) ? 2 
                     }
                     const int q = 32 * u + 16 * c2 + m;
                     const int o = q * 32 + ((g ^ fwr_dperm(q)) << 3);
-                    *reinterpret_cast<half8*>(db + o) = oh;
-                    *reinterpret_cast<half8*>(db + 4096 + o) = ol;
+                    *reinterpret_cast<s3d_half8*>(db + o) = oh;
+                    *reinterpret_cast<s3d_half8*>(db + 4096 + o) = ol;
                 }
             }
         }
@@ -656,7 +605,7 @@ __global__ __launch_bounds__(PIPE_THREADS, (PIPE_R == 2 && PIPE_WAVES == 4) ? 2 
             }
             if ((MODE == 2 || MODE == 3) && (j & 1)) store_pair(ta.Uout, r, j >> 1, y[j - 1], y[j]);
         }
-        const float mean = quad_sum16(s) * (1.f / 128.f);
+        const float mean = quad_sum(s) * (1.f / 128.f);
         float v = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
@@ -665,7 +614,7 @@ __global__ __launch_bounds__(PIPE_THREADS, (PIPE_R == 2 && PIPE_WAVES == 4) ? 2 
                 const float d = y[j][i] - mean;
                 v += d * d;
             }
-        const float rstd = 1.f / sqrtf(quad_sum16(v) * (1.f / 128.f) + 1e-5f);
+        const float rstd = 1.f / sqrtf(quad_sum(v) * (1.f / 128.f) + 1e-5f);
         float dot = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -681,7 +630,7 @@ __global__ __launch_bounds__(PIPE_THREADS, (PIPE_R == 2 && PIPE_WAVES == 4) ? 2 
             }
         }
         if (FINAL) {
-            dot = quad_sum16(dot) + fco_b[0];
+            dot = quad_sum(dot) + fco_b[0];
             if (ge == 0 && row < rows) {
                 const long grp = g_begin + row / S3D_GROUP;
                 const long b = grp / groups_per_batch;
@@ -811,7 +760,7 @@ __global__ void pack_ffn_f16x3_kernel(const float* __restrict__ w1, const float*
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             if (bf16) {
-                dst[t] = __builtin_bit_cast(_Float16, (unsigned short)(bf16_pair(v[t], 0.f) & 0xFFFFu));
+                dst[t] = __builtin_bit_cast(_Float16, (unsigned short)(s3d_bf16_pair(v[t], 0.f) & 0xFFFFu));
                 dst[4096 + t] = (_Float16)0.f;
                 continue;
             }

@@ -16,7 +16,7 @@
 //   phase 3  wave w = output channels 32 w .. 32 w + 31:  u = N xbar + n + x0 (K = 512: 16 k-steps, A = N fragments from
 //            L2, B = xbar fragments from LDS), stored as the rows the final FFN kernel normalises in its prologue.
 //
-// Every accumulator adds its products in the order of the row-GEMM kernels it replaces (k ascending; hi*lo, lo*hi, hi*hi;
+// Every accumulator adds its products in the order of the row-GEMM kernels it replaces (k ascending; s3d_mfma3's product order;
 // then + bias, then + residual) and the mixing step is the same code: the u rows are BIT-IDENTICAL to the four-launch
 // form (tests/test_gpu_parity.py::test_fused_last_layer_is_bit_identical).
 //
@@ -26,8 +26,6 @@
 // from HBM.
 #include "decode.h"
 #include "attn_last.h"
-
-typedef _Float16 lhalf8 __attribute__((ext_vector_type(8)));
 
 #define AL_QS (2048 + 16)   // bytes per query region
 #ifndef AL_D1
@@ -103,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void attn_last_fused_kernel(const float* __
 #pragma unroll 1
     for (long it = blockIdx.x; it < n_it; it += gridDim.x) {
         // the x0 tile (requested an iteration ago) becomes f16 hi | lo B fragments
-        lhalf8 xh[NG][4], xl[NG][4];
+        s3d_half8 xh[NG][4], xl[NG][4];
 #pragma unroll
         for (int ng = 0; ng < NG; ++ng)
 #pragma unroll
@@ -112,8 +110,8 @@ __global__ __launch_bounds__(256, 2) void attn_last_fused_kernel(const float* __
                                     v1[ng][u][0], v1[ng][u][1], v1[ng][u][2], v1[ng][u][3]};
                 s3d_half8 h, l;
                 s3d_split8(x, h, l);
-                xh[ng][u] = __builtin_bit_cast(lhalf8, h);
-                xl[ng][u] = __builtin_bit_cast(lhalf8, l);
+                xh[ng][u] = __builtin_bit_cast(s3d_half8, h);
+                xl[ng][u] = __builtin_bit_cast(s3d_half8, l);
             }
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_sched_barrier(0);
@@ -128,11 +126,11 @@ __global__ __launch_bounds__(256, 2) void attn_last_fused_kernel(const float* __
             // Weight fragments through a register ring D1 k-steps deep (32 steps: 8 output tiles x 4 k-steps; hi | lo of a step = 8
             // registers).  A step is 6 MFMAs (~100 cycles) and a fragment comes from L2 (600+ cycles under load).
             constexpr int D1 = AL_D1;
-            lhalf8 wh[D1], wl[D1];
+            s3d_half8 wh[D1], wl[D1];
 #pragma unroll
             for (int st = 0; st < D1; ++st) {
-                wh[st] = *reinterpret_cast<const lhalf8*>(wp + (loff + (unsigned)st * 2048u));
-                if (!SINGLE) wl[st] = *reinterpret_cast<const lhalf8*>(wp + (loff + (unsigned)st * 2048u + 1024u));
+                wh[st] = *reinterpret_cast<const s3d_half8*>(wp + (loff + (unsigned)st * 2048u));
+                if (!SINGLE) wl[st] = *reinterpret_cast<const s3d_half8*>(wp + (loff + (unsigned)st * 2048u + 1024u));
             }
             f32x4 acc[NG];
 #pragma unroll
@@ -156,8 +154,8 @@ __global__ __launch_bounds__(256, 2) void attn_last_fused_kernel(const float* __
                     acc[ng] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[sl], xh[ng][u], acc[ng], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if (st + D1 < 32) {   // the slot is free: step st + D1
-                    wh[sl] = *reinterpret_cast<const lhalf8*>(wp + (loff + (unsigned)(st + D1) * 2048u));
-                    if (!SINGLE) wl[sl] = *reinterpret_cast<const lhalf8*>(wp + (loff + (unsigned)(st + D1) * 2048u + 1024u));
+                    wh[sl] = *reinterpret_cast<const s3d_half8*>(wp + (loff + (unsigned)(st + D1) * 2048u));
+                    if (!SINGLE) wl[sl] = *reinterpret_cast<const s3d_half8*>(wp + (loff + (unsigned)(st + D1) * 2048u + 1024u));
                 }
                 if (u == 3) {
                     const int co = (8 * wave + j) * 16 + 4 * g;
@@ -203,25 +201,25 @@ __global__ __launch_bounds__(256, 2) void attn_last_fused_kernel(const float* __
             unsigned loff = (unsigned)lane * 16u;
             asm volatile("" : "+v"(loff));
             constexpr int D3 = AL_D3;
-            lhalf8 wh[D3][2], wl[D3][2];   // [ring slot][nt]: see phase 1
+            s3d_half8 wh[D3][2], wl[D3][2];   // [ring slot][nt]: see phase 1
 #pragma unroll
             for (int u = 0; u < D3; ++u)
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
                     const unsigned fo = loff + (unsigned)(nt * 16 + u) * 2048u;
-                    wh[u][nt] = *reinterpret_cast<const lhalf8*>(wp + fo);
-                    if (!SINGLE) wl[u][nt] = *reinterpret_cast<const lhalf8*>(wp + (fo + 1024u));
+                    wh[u][nt] = *reinterpret_cast<const s3d_half8*>(wp + fo);
+                    if (!SINGLE) wl[u][nt] = *reinterpret_cast<const s3d_half8*>(wp + (fo + 1024u));
                 }
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
                 const int sl = u % D3;
                 __builtin_amdgcn_sched_barrier(0);
-                lhalf8 bh[NG], bl[NG];
+                s3d_half8 bh[NG], bl[NG];
 #pragma unroll
                 for (int ng = 0; ng < NG; ++ng) {
                     const unsigned char* f = s_q + (ng * 16 + m) * AL_QS + u * 128 + g * 16;
-                    bh[ng] = *reinterpret_cast<const lhalf8*>(f);
-                    if (!SINGLE) bl[ng] = *reinterpret_cast<const lhalf8*>(f + 64);
+                    bh[ng] = *reinterpret_cast<const s3d_half8*>(f);
+                    if (!SINGLE) bl[ng] = *reinterpret_cast<const s3d_half8*>(f + 64);
                 }
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
@@ -242,8 +240,8 @@ __global__ __launch_bounds__(256, 2) void attn_last_fused_kernel(const float* __
 #pragma unroll
                     for (int nt = 0; nt < 2; ++nt) {
                         const unsigned fo = loff + (unsigned)(nt * 16 + u + D3) * 2048u;
-                        wh[sl][nt] = *reinterpret_cast<const lhalf8*>(wp + fo);
-                        if (!SINGLE) wl[sl][nt] = *reinterpret_cast<const lhalf8*>(wp + (fo + 1024u));
+                        wh[sl][nt] = *reinterpret_cast<const s3d_half8*>(wp + fo);
+                        if (!SINGLE) wl[sl][nt] = *reinterpret_cast<const s3d_half8*>(wp + (fo + 1024u));
                     }
                 }
             }

@@ -14,11 +14,6 @@
 // workgroups where the grid would not fill the chip); wider heads (256 tokens and fewer) stay on the kernels of ldm_ops.hip.
 #include "ldm_ops.h"
 
-typedef _Float16 lh8 __attribute__((ext_vector_type(8)));
-typedef _Float16 lh2 __attribute__((ext_vector_type(2)));
-typedef float lf2 __attribute__((ext_vector_type(2)));
-typedef unsigned lu4 __attribute__((ext_vector_type(4)));
-
 #define LA_KB 64                 // keys per block
 #define LA_KLD 32                // halfs per K row (64 B); its four 16-byte quarters are XOR-swizzled by (key >> 1) & 3:
                                  // conflict-free fragment reads without padding (conv.hip), 22 KiB per block image ->
@@ -61,7 +56,7 @@ __global__ __launch_bounds__(256) void la_pack_kernel(const float* __restrict__ 
     const float scale = 1.f / sqrtf(sqrtf((float)CH));
     const float* base = qkv + (long)n * T * C3 + hh * 3 * CH;
     _Float16* dst = img + b * G::IMG;
-    for (int i = threadIdx.x; i < G::IMG / 8; i += 256) *reinterpret_cast<lu4*>(dst + 8 * i) = lu4{0u, 0u, 0u, 0u};
+    for (int i = threadIdx.x; i < G::IMG / 8; i += 256) *reinterpret_cast<s3d_uint4*>(dst + 8 * i) = s3d_uint4{0u, 0u, 0u, 0u};
     __syncthreads();
     if (G::SPARE && threadIdx.x < LA_KB) {
         // spare channel CH of the K rows: 0 for a key, -30000 for a key slot beyond T (q carries 1 there: the score of a
@@ -78,7 +73,7 @@ __global__ __launch_bounds__(256) void la_pack_kernel(const float* __restrict__ 
         const float* row = base + (long)kg * C3;
         const f32x4 ka = ld4(row + CH + c0), kc = ld4(row + CH + c0 + 4);
         const f32x4 va = ld4(row + 2 * CH + c0), vc = ld4(row + 2 * CH + c0 + 4);
-        lh8 h, m, l;
+        s3d_half8 h, m, l;
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             _Float16 a, bb, c;
@@ -88,9 +83,9 @@ __global__ __launch_bounds__(256) void la_pack_kernel(const float* __restrict__ 
             l[t] = c;
         }
         const int ko = (c0 >> 5) * 3 * LA_K_PART + key * LA_KLD + LA_KSWZ(key, (c0 >> 3) & 3);
-        *reinterpret_cast<lh8*>(dst + ko) = h;
-        *reinterpret_cast<lh8*>(dst + LA_K_PART + ko) = m;
-        *reinterpret_cast<lh8*>(dst + 2 * LA_K_PART + ko) = l;
+        *reinterpret_cast<s3d_half8*>(dst + ko) = h;
+        *reinterpret_cast<s3d_half8*>(dst + LA_K_PART + ko) = m;
+        *reinterpret_cast<s3d_half8*>(dst + 2 * LA_K_PART + ko) = l;
         // key = 16 kt + 4 g' + i  ->  slot 32 (kt >> 1) + 8 g' + 4 (kt & 1) + i   (the order P^T is produced in)
         const int kt = key >> 4, slot = 32 * (kt >> 1) + 8 * ((key >> 2) & 3) + 4 * (kt & 1) + (key & 3);
         _Float16* v0 = dst + G::V_OFF + c0 * LA_VLD + slot;
@@ -104,30 +99,6 @@ __global__ __launch_bounds__(256) void la_pack_kernel(const float* __restrict__ 
     }
 }
 
-// hi/lo split of a pair: v_cvt_pk_f16_f32 + v_fma_mixlo/hi_f16 (see decode_attnq.hip)
-__device__ __forceinline__ void la_split2(float a, float b, unsigned& hi, unsigned& lo) {
-    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(lf2{a, b}, lh2));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(a));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(b));
-}
-__device__ __forceinline__ void la_swap32(float& x, float& y) { asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y)); }
-__device__ __forceinline__ void la_swap16(float& x, float& y) { asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y)); }
-__device__ __forceinline__ float la_colmax(float v) {   // max over the 4 lane groups g of one query column
-    float x = v, y = v;
-    la_swap32(x, y);
-    x = fmaxf(x, y);
-    y = x;
-    la_swap16(x, y);
-    return fmaxf(x, y);
-}
-__device__ __forceinline__ float la_colsum(float v) {
-    float x = v, y = v;
-    la_swap32(x, y);
-    x += y;
-    y = x;
-    la_swap16(x, y);
-    return x + y;
-}
 #define LA_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
 
 // QT: 16-query tiles per wave (2: every fragment read feeds two tiles; 1: twice the workgroups, for grids that would not
@@ -156,14 +127,13 @@ __global__ __launch_bounds__(256, 3) void la_attention_kernel(const float* __res
         for (int i = 0; i < (G::PIECES + 3) / 4; ++i) {
             const int piece = wave + 4 * i;
             if (piece < G::PIECES)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + piece * 512 + lane * 8),
-                                                 (__attribute__((address_space(3))) void*)(buf + piece * 512), 16, 0, 0);
+                S3D_DMA_PIECE(src + piece * 512 + lane * 8, buf + piece * 512, 0);
         }
     };
     dma_block(0, s_b0);
 
     // the wave's 2 x 16 queries: q (scaled) split three ways, k-slot 8g + t <-> channel 8g + t
-    lh8 qh[QT], qm[QT], ql[QT];
+    s3d_half8 qh[QT], qm[QT], ql[QT];
     int qrow[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
@@ -198,25 +168,22 @@ __global__ __launch_bounds__(256, 3) void la_attention_kernel(const float* __res
     // fragments of two key tiles, waits lgkmcnt(0), multiplies, and only then reads the next two — the LDS latency is
     // exposed five times per block.  Here the block's 12 K fragments are requested up front, the V^T fragments under the
     // S^T products and the softmax.
-#define LA_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-#define LA_WAIT6(n, a, b, c, d, e, f) asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f) : "n"(n))
-#define LA_WAIT4(n, a, b, c, d) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(n))
     auto compute = [&](const _Float16* buf, int k0) {
         const bool partial = k0 + LA_KB > T;
         const unsigned lk = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(const_cast<_Float16*>(buf) + m * LA_KLD + LA_KSWZ(m, g));   // key tile kt adds 16 rows: same swizzle
         const unsigned lv = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(const_cast<_Float16*>(buf) + 3 * LA_K_PART + m * LA_VLD + 8 * g);
-        lh8 kf[4][3];        // [key tile][hi, mid, lo]
-        lh8 vf[2][DT][2];    // [k-step][dim tile][hi, lo]
+        s3d_half8 kf[4][3];        // [key tile][hi, mid, lo]
+        s3d_half8 vf[2][DT][2];    // [k-step][dim tile][hi, lo]
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
-            for (int pt = 0; pt < 3; ++pt) LA_RD(kf[kt][pt], lk, (kt * 16 * LA_KLD + pt * LA_K_PART) * 2);
+            for (int pt = 0; pt < 3; ++pt) S3D_DS_READ(kf[kt][pt], lk, (kt * 16 * LA_KLD + pt * LA_K_PART) * 2);
         // ---- S^T for the 4 key tiles x QT query tiles: six products, the unscaled four into one accumulator ----
         f32x4 s[QT][4];
 #pragma unroll
         for (int kp = 0; kp < 2; ++kp) {
-            if (kp == 0) LA_WAIT6(6, kf[0][0], kf[0][1], kf[0][2], kf[1][0], kf[1][1], kf[1][2]);
-            else LA_WAIT6(2 * DT, kf[2][0], kf[2][1], kf[2][2], kf[3][0], kf[3][1], kf[3][2]);   // the V^T reads of k-step 0 stay in flight
+            if (kp == 0) S3D_LGKM_WAIT6(6, kf[0][0], kf[0][1], kf[0][2], kf[1][0], kf[1][1], kf[1][2]);
+            else S3D_LGKM_WAIT6(2 * DT, kf[2][0], kf[2][1], kf[2][2], kf[3][0], kf[3][1], kf[3][2]);   // the V^T reads of k-step 0 stay in flight
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2) {
                 const int kt = 2 * kp + k2;
@@ -236,11 +203,11 @@ __global__ __launch_bounds__(256, 3) void la_attention_kernel(const float* __res
 #pragma unroll
             for (int d = 0; d < DT; ++d)
 #pragma unroll
-                for (int pt = 0; pt < 2; ++pt) LA_RD(vf[kp][d][pt], lv, (16 * d * LA_VLD + 32 * kp + pt * G::V_PART) * 2);
+                for (int pt = 0; pt < 2; ++pt) S3D_DS_READ(vf[kp][d][pt], lv, (16 * d * LA_VLD + 32 * kp + pt * G::V_PART) * 2);
         }
         // ---- online softmax over the block's 64 keys; P is produced scaled by 2^14 (exponent bias, removed with 1/den at
         //      the end): small probabilities would otherwise sit in f16's subnormal range and lose their low half ----
-        lh8 ph[QT][2], pl[QT][2];   // [query tile][k-step of the P V product]
+        s3d_half8 ph[QT][2], pl[QT][2];   // [query tile][k-step of the P V product]
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             if (!G::SPARE && partial) {
@@ -254,7 +221,7 @@ __global__ __launch_bounds__(256, 3) void la_attention_kernel(const float* __res
 #pragma unroll
             for (int kt = 1; kt < 4; ++kt)
                 bmax = fmaxf(bmax, fmaxf(fmaxf(s[qt][kt][0], s[qt][kt][1]), fmaxf(s[qt][kt][2], s[qt][kt][3])));
-            bmax = la_colmax(bmax);
+            bmax = s3d_colmax16(bmax);
             const float mnew = fmaxf(mx[qt], bmax);
             const float corr = __builtin_amdgcn_exp2f(mx[qt] - mnew);
             mx[qt] = mnew;
@@ -272,24 +239,15 @@ __global__ __launch_bounds__(256, 3) void la_attention_kernel(const float* __res
             for (int d = 0; d < DT; ++d) acc[d][qt] *= corr;
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
-                unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-                la_split2(s[qt][2 * kk][0], s[qt][2 * kk][1], h0, l0);
-                la_split2(s[qt][2 * kk][2], s[qt][2 * kk][3], h1, l1);
-                la_split2(s[qt][2 * kk + 1][0], s[qt][2 * kk + 1][1], h2, l2);
-                la_split2(s[qt][2 * kk + 1][2], s[qt][2 * kk + 1][3], h3, l3);
-                ph[qt][kk] = __builtin_bit_cast(lh8, lu4{h0, h1, h2, h3});
-                pl[qt][kk] = __builtin_bit_cast(lh8, lu4{l0, l1, l2, l3});
+                s3d_split8(s[qt][2 * kk], s[qt][2 * kk + 1], ph[qt][kk], pl[qt][kk]);
             }
         }
-        // partial-register asm writes -> MFMA reads: pad (decode_attnq.hip, AQ_SETTLE)
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_nop 15" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        S3D_SPLIT_SETTLE();   // partial-register asm writes -> MFMA reads
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             if (DT == 2) {
-                if (kk == 0) LA_WAIT4(4, vf[0][0][0], vf[0][0][1], vf[0][1][0], vf[0][1][1]);
-                else LA_WAIT4(0, vf[1][0][0], vf[1][0][1], vf[1][1][0], vf[1][1][1]);
+                if (kk == 0) S3D_LGKM_WAIT4(4, vf[0][0][0], vf[0][0][1], vf[0][1][0], vf[0][1][1]);
+                else S3D_LGKM_WAIT4(0, vf[1][0][0], vf[1][0][1], vf[1][1][0], vf[1][1][1]);
             } else {
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vf[0][0][0]), "+v"(vf[0][0][1]), "+v"(vf[1][0][0]), "+v"(vf[1][0][1]));
             }
@@ -297,9 +255,7 @@ __global__ __launch_bounds__(256, 3) void la_attention_kernel(const float* __res
             for (int d = 0; d < DT; ++d)
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) {
-                    f32x4 o = LA_MFMA(vf[kk][d][0], pl[qt][kk], acc[d][qt]);
-                    o = LA_MFMA(vf[kk][d][1], ph[qt][kk], o);
-                    acc[d][qt] = LA_MFMA(vf[kk][d][0], ph[qt][kk], o);
+                    acc[d][qt] = s3d_mfma3(vf[kk][d][0], vf[kk][d][1], ph[qt][kk], pl[qt][kk], acc[d][qt]);
                 }
         }
     };
@@ -319,7 +275,7 @@ __global__ __launch_bounds__(256, 3) void la_attention_kernel(const float* __res
         // den carries the same 2^14 as P.  With a spare V^T row it is row CH of O^T: element CH % 4 of the last tile's
         // accumulator in lane group (CH % 16) / 4; the other groups hold 0 there after the select
         const float dsel = G::SPARE ? (g == (CH % 16) / 4 ? acc[DT - 1][qt][CH % 4] : 0.f) : den[qt];
-        const float inv = 1.f / la_colsum(dsel);
+        const float inv = 1.f / s3d_colsum16(dsel);
         if (qrow[qt] < T) {
             float* o = out + ((long)n * T + qrow[qt]) * (heads * CH) + hh * CH;
 #pragma unroll
@@ -364,13 +320,12 @@ __global__ __launch_bounds__(256, 2) void la_attention2_kernel(const float* __re
         for (int i = 0; i < (G::PIECES + 3) / 4; ++i) {
             const int piece = wave + 4 * i;
             if (piece < G::PIECES)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + piece * 512 + lane * 8),
-                                                 (__attribute__((address_space(3))) void*)(buf + piece * 512), 16, 0, 0);
+                S3D_DMA_PIECE(src + piece * 512 + lane * 8, buf + piece * 512, 0);
         }
     };
     dma_block(kb_lo, s_b0);
 
-    lh8 qh[QT][KS], qm[QT][KS], ql[QT][KS];
+    s3d_half8 qh[QT][KS], qm[QT][KS], ql[QT][KS];
     int qrow[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
@@ -407,14 +362,14 @@ __global__ __launch_bounds__(256, 2) void la_attention2_kernel(const float* __re
         const bool partial = k0 + LA_KB > T;
         const unsigned lk = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(const_cast<_Float16*>(buf) + m * LA_KLD + LA_KSWZ(m, g));
         const unsigned lv = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(const_cast<_Float16*>(buf) + G::V_OFF + m * LA_VLD + 8 * g);
-        lh8 kf[2][KS][3];    // [ring slot][k-step][hi, mid, lo]
-        lh8 vf[2][DT][2];    // [k-step of P V][dim tile][hi, lo]
+        s3d_half8 kf[2][KS][3];    // [ring slot][k-step][hi, mid, lo]
+        s3d_half8 vf[2][DT][2];    // [k-step of P V][dim tile][hi, lo]
 #define LA_RDK(slot, kt)                                                                                              \
     _Pragma("unroll") for (int ks = 0; ks < KS; ++ks) _Pragma("unroll") for (int pt = 0; pt < 3; ++pt)                \
-        LA_RD(kf[slot][ks][pt], lk, ((kt) * 16 * LA_KLD + (3 * ks + pt) * LA_K_PART) * 2)
+        S3D_DS_READ(kf[slot][ks][pt], lk, ((kt) * 16 * LA_KLD + (3 * ks + pt) * LA_K_PART) * 2)
 #define LA_RDV(kk)                                                                                                    \
     _Pragma("unroll") for (int d = 0; d < DT; ++d) _Pragma("unroll") for (int pt = 0; pt < 2; ++pt)                   \
-        LA_RD(vf[kk][d][pt], lv, (16 * d * LA_VLD + 32 * (kk) + pt * G::V_PART) * 2)
+        S3D_DS_READ(vf[kk][d][pt], lv, (16 * d * LA_VLD + 32 * (kk) + pt * G::V_PART) * 2)
         LA_RDK(0, 0);
         LA_RDK(1, 1);
         f32x4 s[QT][4];
@@ -422,7 +377,7 @@ __global__ __launch_bounds__(256, 2) void la_attention2_kernel(const float* __re
         for (int kt = 0; kt < 4; ++kt) {
             const int sl = kt & 1;
             // twelve reads in flight at most (the counter holds 15): the oldest six are this key tile's
-            LA_WAIT6(6, kf[sl][0][0], kf[sl][0][1], kf[sl][0][2], kf[sl][1][0], kf[sl][1][1], kf[sl][1][2]);
+            S3D_LGKM_WAIT6(6, kf[sl][0][0], kf[sl][0][1], kf[sl][0][2], kf[sl][1][0], kf[sl][1][1], kf[sl][1][2]);
 #pragma unroll
             for (int qt = 0; qt < QT; ++qt) {
                 f32x4 a2 = LA_MFMA(kf[sl][0][0], ql[qt][0], zero4());
@@ -445,7 +400,7 @@ __global__ __launch_bounds__(256, 2) void la_attention2_kernel(const float* __re
             else if (kt == 2) { LA_RDV(0); }
             else { LA_RDV(1); }
         }
-        lh8 ph[QT][2], pl[QT][2];
+        s3d_half8 ph[QT][2], pl[QT][2];
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             if (partial) {
@@ -459,7 +414,7 @@ __global__ __launch_bounds__(256, 2) void la_attention2_kernel(const float* __re
 #pragma unroll
             for (int kt = 1; kt < 4; ++kt)
                 bmax = fmaxf(bmax, fmaxf(fmaxf(s[qt][kt][0], s[qt][kt][1]), fmaxf(s[qt][kt][2], s[qt][kt][3])));
-            bmax = la_colmax(bmax);
+            bmax = s3d_colmax16(bmax);
             const float mnew = fmaxf(mx[qt], bmax);
             const float corr = __builtin_amdgcn_exp2f(mx[qt] - mnew);
             mx[qt] = mnew;
@@ -477,29 +432,19 @@ __global__ __launch_bounds__(256, 2) void la_attention2_kernel(const float* __re
             for (int d = 0; d < DT; ++d) acc[d][qt] *= corr;
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
-                unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-                la_split2(s[qt][2 * kk][0], s[qt][2 * kk][1], h0, l0);
-                la_split2(s[qt][2 * kk][2], s[qt][2 * kk][3], h1, l1);
-                la_split2(s[qt][2 * kk + 1][0], s[qt][2 * kk + 1][1], h2, l2);
-                la_split2(s[qt][2 * kk + 1][2], s[qt][2 * kk + 1][3], h3, l3);
-                ph[qt][kk] = __builtin_bit_cast(lh8, lu4{h0, h1, h2, h3});
-                pl[qt][kk] = __builtin_bit_cast(lh8, lu4{l0, l1, l2, l3});
+                s3d_split8(s[qt][2 * kk], s[qt][2 * kk + 1], ph[qt][kk], pl[qt][kk]);
             }
         }
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_nop 15" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        S3D_SPLIT_SETTLE();
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            if (kk == 0) LA_WAIT6(6, vf[0][0][0], vf[0][0][1], vf[0][1][0], vf[0][1][1], vf[0][2][0], vf[0][2][1]);
-            else LA_WAIT6(0, vf[1][0][0], vf[1][0][1], vf[1][1][0], vf[1][1][1], vf[1][2][0], vf[1][2][1]);
+            if (kk == 0) S3D_LGKM_WAIT6(6, vf[0][0][0], vf[0][0][1], vf[0][1][0], vf[0][1][1], vf[0][2][0], vf[0][2][1]);
+            else S3D_LGKM_WAIT6(0, vf[1][0][0], vf[1][0][1], vf[1][1][0], vf[1][1][1], vf[1][2][0], vf[1][2][1]);
 #pragma unroll
             for (int d = 0; d < DT; ++d)
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) {
-                    f32x4 o = LA_MFMA(vf[kk][d][0], pl[qt][kk], acc[d][qt]);
-                    o = LA_MFMA(vf[kk][d][1], ph[qt][kk], o);
-                    acc[d][qt] = LA_MFMA(vf[kk][d][0], ph[qt][kk], o);
+                    acc[d][qt] = s3d_mfma3(vf[kk][d][0], vf[kk][d][1], ph[qt][kk], pl[qt][kk], acc[d][qt]);
                 }
         }
 #undef LA_RDK
@@ -518,7 +463,7 @@ __global__ __launch_bounds__(256, 2) void la_attention2_kernel(const float* __re
     }
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
-        const float dsum = la_colsum(den[qt]);   // den and acc carry the same 2^14
+        const float dsum = s3d_colsum16(den[qt]);   // den and acc carry the same 2^14
         if (qrow[qt] >= T) continue;
         if (nsplit == 1) {
             const float inv = 1.f / dsum;
@@ -561,10 +506,6 @@ __global__ __launch_bounds__(256) void la_merge_kernel(const float* __restrict__
     }
     st4(out + r * CH + c, o * (1.f / d));
 }
-
-#undef LA_RD
-#undef LA_WAIT6
-#undef LA_WAIT4
 
 // key splits of the wide-head kernel: enough workgroups for two per CU, at least two key blocks per split (measured at
 // 1 x 1 024 x 8 heads: 2 / 4 / 8 splits 27.2 / 27.8 / 32.4 us per call against 44.7 us for the fp32-MFMA kernel;

@@ -163,7 +163,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const WgradArgs a, in
 // [channel][row] LDS tile (80-byte channel stride: conflict-free for both the writes and the fragment
 // reads).  Next step's global loads are issued before the MFMAs of the current one.
 // ---------------------------------------------------------------------------------------------
-typedef _Float16 wl_half8 __attribute__((ext_vector_type(8)));
 #define WL_LD 40     // (a 96-byte stride makes the b128 fragment reads conflict-free but the stores slower: measured no gain)
 #define WZ_LD 40
 __global__ __launch_bounds__(256) void wgrad_lin_f16x3_kernel(const WgradArgs a, int n_cblk, long P,
@@ -247,18 +246,18 @@ __global__ __launch_bounds__(256) void wgrad_lin_f16x3_kernel(const WgradArgs a,
         }
         __syncthreads();
         if (it + 1 < steps_per_split) gload(p_begin + (long)(it + 1) * 32);
-        wl_half8 ah[4], al[4], bh[4], bl[4];
+        s3d_half8 ah[4], al[4], bh[4], bl[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int o = (64 * wn + 16 * i + m) * WL_LD + 8 * g;
-            ah[i] = *reinterpret_cast<const wl_half8*>(&s_t[0][0][o]);
-            al[i] = *reinterpret_cast<const wl_half8*>(&s_t[0][1][o]);
+            ah[i] = *reinterpret_cast<const s3d_half8*>(&s_t[0][0][o]);
+            al[i] = *reinterpret_cast<const s3d_half8*>(&s_t[0][1][o]);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int o = (64 * wc + 16 * j + m) * WL_LD + 8 * g;
-            bh[j] = *reinterpret_cast<const wl_half8*>(&s_t[1][0][o]);
-            bl[j] = *reinterpret_cast<const wl_half8*>(&s_t[1][1][o]);
+            bh[j] = *reinterpret_cast<const s3d_half8*>(&s_t[1][0][o]);
+            bl[j] = *reinterpret_cast<const s3d_half8*>(&s_t[1][1][o]);
         }
         // three product kinds, each swept over the 16 independent accumulators (a.single, the S3D_PREC_F16 training throughput
         // mode: the hi * hi sweep alone — a uniform branch; this kernel is bound by its operand staging, not by its MFMAs)
@@ -324,20 +323,12 @@ __global__ void colsum_final_kernel(const float* __restrict__ partial, int nchun
 // the other buffer in flight hipcc guards compiler-generated ds_reads of the same object with s_waitcnt vmcnt(0) — the
 // wait the double buffer exists to avoid — and splitting the buffers into separate objects (an unrolled two-step loop)
 // made it shuffle and spill the accumulators.  LDS returns in order: lgkmcnt(n) leaves exactly the n youngest reads out.
-#define FWR_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-#define FWR_WAIT4(n, r0, r1, r2, r3) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) : "n"(n))
-#define FWR_WAIT2(n, r0, r1) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(r0), "+v"(r1) : "n"(n))
 #define FWR_BUF_BYTES (4 * FWR_BLK_HALFS)   // one buffer: D^T image (16 KiB) | R image (16 KiB)
 
 // one block image (16 KiB) -> LDS: wave w copies the 4 KiB at offset 4096 w as four 1-KiB LDS-DMA instructions that
 // differ only in their immediate offset (one lane address, one M0 value per image)
 __device__ __forceinline__ void fwr_dma(const _Float16* gblk, _Float16* lbuf, int wave, int lane) {
-    const __attribute__((address_space(1))) void* g = (const __attribute__((address_space(1))) void*)(gblk + wave * 2048 + lane * 8);
-    __attribute__((address_space(3))) void* l = (__attribute__((address_space(3))) void*)(lbuf + wave * 2048);
-    __builtin_amdgcn_global_load_lds(g, l, 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(g, l, 16, 1024, 0);
-    __builtin_amdgcn_global_load_lds(g, l, 16, 2048, 0);
-    __builtin_amdgcn_global_load_lds(g, l, 16, 3072, 0);
+    s3d_dma_pieces<4>(gblk + wave * 2048 + lane * 8, lbuf + wave * 2048);
 }
 
 // SINGLE (round 6, the training step's single-pass f16 throughput mode, S3D_PREC_F16): only the hi * hi product of every split
@@ -371,7 +362,7 @@ __global__ __launch_bounds__(256, 2) void ffn_wgrad_rec_kernel(const FfnWgradArg
     const _Float16* rimg = reinterpret_cast<const _Float16*>(a.Rimg) + blk0 * FWR_BLK_HALFS;
 
     // this wave's W fragments: hidden tiles 2*wave + e of the block, K = 128 = 4 x 32
-    wl_half8 wh[2][4], wlo[2][4];
+    s3d_half8 wh[2][4], wlo[2][4];
     float bv[2];
     {
         const _Float16* img = reinterpret_cast<const _Float16*>(a.wimg);
@@ -381,8 +372,8 @@ __global__ __launch_bounds__(256, 2) void ffn_wgrad_rec_kernel(const FfnWgradArg
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const size_t o = ((size_t)(tile * 4 + u) * 64 + lane) * 8;
-                wh[e][u] = *reinterpret_cast<const wl_half8*>(img + o);
-                wlo[e][u] = SINGLE ? wh[e][u] : *reinterpret_cast<const wl_half8*>(img + (size_t)S3D_FFN * 128 + o);
+                wh[e][u] = *reinterpret_cast<const s3d_half8*>(img + o);
+                wlo[e][u] = SINGLE ? wh[e][u] : *reinterpret_cast<const s3d_half8*>(img + (size_t)S3D_FFN * 128 + o);
             }
             bv[e] = a.bias ? a.bias[tile * 16 + m] : 0.f;
         }
@@ -434,15 +425,15 @@ __global__ __launch_bounds__(256, 2) void ffn_wgrad_rec_kernel(const FfnWgradArg
         for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
             for (int e = 0; e < 2; ++e) z[rt][e] = f32x4{bv[e], bv[e], bv[e], bv[e]};
-        wl_half8 ah[2], al[2];
+        s3d_half8 ah[2], al[2];
         {
-            wl_half8 xh[2][2], xl[2][2];
+            s3d_half8 xh[2][2], xl[2][2];
             {
                 const unsigned xa = x_addr0[0] + boff;
                 if (SINGLE) {
-                    FWR_READ(xh[0][0], xa, 0); FWR_READ(xh[0][1], xa, 4096);
+                    S3D_DS_READ(xh[0][0], xa, 0); S3D_DS_READ(xh[0][1], xa, 4096);
                 } else {
-                    FWR_READ(xh[0][0], xa, 0); FWR_READ(xl[0][0], xa, 8192); FWR_READ(xh[0][1], xa, 4096); FWR_READ(xl[0][1], xa, 12288);
+                    S3D_DS_READ(xh[0][0], xa, 0); S3D_DS_READ(xl[0][0], xa, 8192); S3D_DS_READ(xh[0][1], xa, 4096); S3D_DS_READ(xl[0][1], xa, 12288);
                 }
             }
 #pragma unroll
@@ -451,19 +442,19 @@ __global__ __launch_bounds__(256, 2) void ffn_wgrad_rec_kernel(const FfnWgradArg
                 if (SINGLE) {   // (half the reads: the counted waits leave the next step's two / the A fragment's one outstanding)
                     if (u < 3) {
                         const unsigned xa = x_addr0[u + 1] + boff;
-                        FWR_READ(xh[ns][0], xa, 0); FWR_READ(xh[ns][1], xa, 4096);
-                        FWR_WAIT2(2, xh[cs][0], xh[cs][1]);
+                        S3D_DS_READ(xh[ns][0], xa, 0); S3D_DS_READ(xh[ns][1], xa, 4096);
+                        S3D_LGKM_WAIT2(2, xh[cs][0], xh[cs][1]);
                     } else {
-                        FWR_READ(ah[0], aa, 0);
-                        FWR_WAIT2(1, xh[cs][0], xh[cs][1]);
+                        S3D_DS_READ(ah[0], aa, 0);
+                        S3D_LGKM_WAIT2(1, xh[cs][0], xh[cs][1]);
                     }
                 } else if (u < 3) {
                     const unsigned xa = x_addr0[u + 1] + boff;
-                    FWR_READ(xh[ns][0], xa, 0); FWR_READ(xl[ns][0], xa, 8192); FWR_READ(xh[ns][1], xa, 4096); FWR_READ(xl[ns][1], xa, 12288);
-                    FWR_WAIT4(4, xh[cs][0], xl[cs][0], xh[cs][1], xl[cs][1]);
+                    S3D_DS_READ(xh[ns][0], xa, 0); S3D_DS_READ(xl[ns][0], xa, 8192); S3D_DS_READ(xh[ns][1], xa, 4096); S3D_DS_READ(xl[ns][1], xa, 12288);
+                    S3D_LGKM_WAIT4(4, xh[cs][0], xl[cs][0], xh[cs][1], xl[cs][1]);
                 } else {
-                    FWR_READ(ah[0], aa, 0); FWR_READ(al[0], aa, 8192);
-                    FWR_WAIT4(2, xh[cs][0], xl[cs][0], xh[cs][1], xl[cs][1]);
+                    S3D_DS_READ(ah[0], aa, 0); S3D_DS_READ(al[0], aa, 8192);
+                    S3D_LGKM_WAIT4(2, xh[cs][0], xl[cs][0], xh[cs][1], xl[cs][1]);
                 }
                 if (!SINGLE) {
 #pragma unroll
@@ -484,7 +475,7 @@ __global__ __launch_bounds__(256, 2) void ffn_wgrad_rec_kernel(const FfnWgradArg
         }
         // activity bit, split: hidden unit (block-local) 32*wave + 16e + m -> bit 4*wave + e + FFN_MASK_POS(m & 3) of dword
         // g' = m >> 2 of the row; this lane's rows are 4g..4g+3 (tile 0) and 16+4g.. (tile 1)
-        wl_half8 zh[2], zl[2];
+        s3d_half8 zh[2], zl[2];
         {
             const uint4 mw0 = *reinterpret_cast<const uint4*>(&s_m[cur][(m >> 2) * 32 + 4 * g]);
             const uint4 mw1 = *reinterpret_cast<const uint4*>(&s_m[cur][(m >> 2) * 32 + 16 + 4 * g]);
@@ -507,16 +498,16 @@ __global__ __launch_bounds__(256, 2) void ffn_wgrad_rec_kernel(const FfnWgradArg
             const int cs = i & 1, ns = cs ^ 1;
             if (SINGLE) {
                 if (i < 7) {
-                    FWR_READ(ah[ns], aa, (i + 1) * 1024);
+                    S3D_DS_READ(ah[ns], aa, (i + 1) * 1024);
                     asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(ah[cs]));
                 } else {
                     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ah[cs]));
                 }
             } else if (i < 7) {
-                FWR_READ(ah[ns], aa, (i + 1) * 1024); FWR_READ(al[ns], aa, (i + 1) * 1024 + 8192);
-                FWR_WAIT2(2, ah[cs], al[cs]);
+                S3D_DS_READ(ah[ns], aa, (i + 1) * 1024); S3D_DS_READ(al[ns], aa, (i + 1) * 1024 + 8192);
+                S3D_LGKM_WAIT2(2, ah[cs], al[cs]);
             } else {
-                FWR_WAIT2(0, ah[cs], al[cs]);
+                S3D_LGKM_WAIT2(0, ah[cs], al[cs]);
             }
             if (!SINGLE) {
 #pragma unroll
@@ -652,9 +643,9 @@ int launch_pack_ffn_rec_f16x3(const float* w, int sh, int sk, float* out, hipStr
 #define W3_XROW 24    // halfs per halo row
 #define W3_XLD 144    // halfs per channel of the X^T tile (6 x 24: 288 B = 32 mod 64)
 typedef int w3_int4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ wl_half8 w3_frag(int d0, int d1, int d2, int d3) {
+__device__ __forceinline__ s3d_half8 w3_frag(int d0, int d1, int d2, int d3) {
     w3_int4 v = {d0, d1, d2, d3};
-    return __builtin_bit_cast(wl_half8, v);
+    return __builtin_bit_cast(s3d_half8, v);
 }
 // WNT x WCT accumulator tile pairs per wave per tap, WVN x WVC waves: block = 16*WNT*WVN (n) x 16*WCT*WVC (c).
 // <2,2,2,2>: 64 x 64 (channel counts that are multiples of 64); <2,1,2,2>: 64 x 32; <1,1,4,1>: 64 x 16 (the 3 -> 16
@@ -739,7 +730,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_conv3_f16x3_kernel(const WgradAr
         {
             const float tvf = (vm & 1u) ? 1.f : 0.f;
             const float dvf = nvalid ? tvf : 0.f;
-            wl_half8 hi, lo;
+            s3d_half8 hi, lo;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float v = pd[j] * dvf;
@@ -747,8 +738,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_conv3_f16x3_kernel(const WgradAr
                 hi[j] = h;
                 lo[j] = (_Float16)(v - (float)h);
             }
-            *reinterpret_cast<wl_half8*>(&s_d[0][ch * W3_DLD + 8 * slot]) = hi;
-            *reinterpret_cast<wl_half8*>(&s_d[1][ch * W3_DLD + 8 * slot]) = lo;
+            *reinterpret_cast<s3d_half8*>(&s_d[0][ch * W3_DLD + 8 * slot]) = hi;
+            *reinterpret_cast<s3d_half8*>(&s_d[1][ch * W3_DLD + 8 * slot]) = lo;
 #pragma unroll
             for (int k = 0; k < XK; ++k) {
                 const float rf = (vm & (2u << k)) ? tvf : 0.f;
@@ -764,8 +755,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_conv3_f16x3_kernel(const WgradAr
                 const _Float16 hl = (_Float16)vl, hr = (_Float16)vr;
                 if (xact[k]) {
                     const int o = xc[k] * W3_XLD + xr[k] * W3_XROW;
-                    *reinterpret_cast<wl_half8*>(&s_x[0][o + 8]) = hi;
-                    *reinterpret_cast<wl_half8*>(&s_x[1][o + 8]) = lo;
+                    *reinterpret_cast<s3d_half8*>(&s_x[0][o + 8]) = hi;
+                    *reinterpret_cast<s3d_half8*>(&s_x[1][o + 8]) = lo;
                     s_x[0][o + 7] = hl;
                     s_x[1][o + 7] = (_Float16)(vl - (float)hl);
                     s_x[0][o + 16] = hr;
@@ -776,19 +767,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_conv3_f16x3_kernel(const WgradAr
         __syncthreads();
         if (t + 1 < t_end) gload(t + 1);
         // ---- 9 taps x (WNT x WCT) tiles ----
-        wl_half8 ah[WNT], al[WNT];
+        s3d_half8 ah[WNT], al[WNT];
 #pragma unroll
         for (int i = 0; i < WNT; ++i) {
             const int o = (16 * (wn * WNT + i) + m) * W3_DLD + 8 * g;
-            ah[i] = *reinterpret_cast<const wl_half8*>(&s_d[0][o]);
-            al[i] = *reinterpret_cast<const wl_half8*>(&s_d[1][o]);
+            ah[i] = *reinterpret_cast<const s3d_half8*>(&s_d[0][o]);
+            al[i] = *reinterpret_cast<const s3d_half8*>(&s_d[1][o]);
         }
 #pragma unroll
         for (int dyi = 0; dyi < 3; ++dyi) {
 #pragma unroll
             for (int j = 0; j < WCT; ++j) {
                 const int o = (16 * (wc * WCT + j) + m) * W3_XLD + (g + dyi) * W3_XROW;
-                wl_half8 bh[3], bl[3];
+                s3d_half8 bh[3], bl[3];
 #pragma unroll
                 for (int hl = 0; hl < 2; ++hl) {
                     const w3_int4 I = *reinterpret_cast<const w3_int4*>(&s_x[hl][o + 8]);
@@ -797,9 +788,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_conv3_f16x3_kernel(const WgradAr
                     const int s01 = __builtin_amdgcn_alignbyte(I[1], I[0], 2);
                     const int s12 = __builtin_amdgcn_alignbyte(I[2], I[1], 2);
                     const int s23 = __builtin_amdgcn_alignbyte(I[3], I[2], 2);
-                    const wl_half8 f0 = w3_frag(__builtin_amdgcn_alignbyte(I[0], Pw, 2), s01, s12, s23);
-                    const wl_half8 f1 = __builtin_bit_cast(wl_half8, I);
-                    const wl_half8 f2 = w3_frag(s01, s12, s23, __builtin_amdgcn_alignbyte(Nw, I[3], 2));
+                    const s3d_half8 f0 = w3_frag(__builtin_amdgcn_alignbyte(I[0], Pw, 2), s01, s12, s23);
+                    const s3d_half8 f1 = __builtin_bit_cast(s3d_half8, I);
+                    const s3d_half8 f2 = w3_frag(s01, s12, s23, __builtin_amdgcn_alignbyte(Nw, I[3], 2));
                     if (hl == 0) {
                         bh[0] = f0; bh[1] = f1; bh[2] = f2;
                     } else {
@@ -810,11 +801,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_conv3_f16x3_kernel(const WgradAr
                 for (int dxi = 0; dxi < 3; ++dxi)
 #pragma unroll
                     for (int i = 0; i < WNT; ++i) {
-                        f32x4 c = acc[dyi * 3 + dxi][i][j];
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[dxi], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[dxi], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[dxi], c, 0, 0, 0);
-                        acc[dyi * 3 + dxi][i][j] = c;
+                        acc[dyi * 3 + dxi][i][j] = s3d_mfma3(ah[i], al[i], bh[dxi], bl[dxi], acc[dyi * 3 + dxi][i][j]);
                     }
             }
         }

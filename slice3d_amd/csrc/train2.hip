@@ -515,9 +515,7 @@ __global__ __launch_bounds__(SBT_THREADS) void sample_bwd_tiled_kernel(const Sam
                 for (int u = 0; u < NU; ++u) {
                     const s3d_half8 fh = *reinterpret_cast<const s3d_half8*>(sw + (u * 4 + kk) * 1024 + lane * 8);
                     const s3d_half8 fl = *reinterpret_cast<const s3d_half8*>(sw + (u * 4 + kk) * 1024 + 512 + lane * 8);
-                    draw[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh, bl, draw[u], 0, 0, 0);
-                    draw[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fl, bh, draw[u], 0, 0, 0);
-                    draw[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh, bh, draw[u], 0, 0, 0);
+                    draw[u] = s3d_mfma3(fh, fl, bh, bl, draw[u]);
                 }
             }
         } else {

@@ -34,24 +34,16 @@ struct AttnBwdArgs {
     DropCfg d0;
 };
 
-typedef _Float16 half2b __attribute__((ext_vector_type(2)));
-typedef float float2b __attribute__((ext_vector_type(2)));
-
 // low / high four halfs of an 8-half operand (no instructions: register sub-ranges)
-__device__ __forceinline__ half4q lo4(const half8q v) { return __builtin_shufflevector(v, v, 0, 1, 2, 3); }
-__device__ __forceinline__ half4q hi4(const half8q v) { return __builtin_shufflevector(v, v, 4, 5, 6, 7); }
+__device__ __forceinline__ s3d_half4 lo4(const s3d_half8 v) { return __builtin_shufflevector(v, v, 0, 1, 2, 3); }
+__device__ __forceinline__ s3d_half4 hi4(const s3d_half8 v) { return __builtin_shufflevector(v, v, 4, 5, 6, 7); }
 // transposed tile of f16 values: D = A * I on the 16-deep MFMA, back to halfs (exact)
-__device__ __forceinline__ half4q transpose16(const half4q a, const half4q ident) {
+__device__ __forceinline__ s3d_half4 transpose16(const s3d_half4 a, const s3d_half4 ident) {
     const f32x4 t = __builtin_amdgcn_mfma_f32_16x16x16f16(a, ident, zero4(), 0, 0, 0);
-    const half2b p0 = __builtin_convertvector(float2b{t[0], t[1]}, half2b);
-    const half2b p1 = __builtin_convertvector(float2b{t[2], t[3]}, half2b);
+    const s3d_half2 p0 = __builtin_convertvector(s3d_float2{t[0], t[1]}, s3d_half2);
+    const s3d_half2 p1 = __builtin_convertvector(s3d_float2{t[2], t[3]}, s3d_half2);
     return __builtin_shufflevector(p0, p1, 0, 1, 2, 3);
 }
-
-#define AQB_SETTLE()                                \
-    __builtin_amdgcn_sched_barrier(0);              \
-    asm volatile("s_nop 15" ::: "memory");          \
-    __builtin_amdgcn_sched_barrier(0);
 
 // SINGLE: S3D_PREC_F16 training throughput mode (round 6): one f16 MFMA per product of the Q / K / V recomputation (the kernel's
 // projection phases, 90 % of its MFMAs).  The 13 x 13 core backward keeps all three products in every mode: dS = P (dP - sum P dP)
@@ -76,9 +68,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const AttnBwdArgs a,
         const int h = ph / 3, part = ph - 3 * h;
         const _Float16* src0 = wimg + (size_t)h * AQ_WIN_HALFS + part * AQ3_SLOT_HALFS;
         const int i = wave + 4 * k;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src0 + i * 512 + lane * 8),
-                                         (__attribute__((address_space(3))) void*)(s_win + buf * AQ3_SLOT_HALFS + i * 512),
-                                         16, 0, 0);
+        S3D_DMA_PIECE(src0 + i * 512 + lane * 8, s_win + buf * AQ3_SLOT_HALFS + i * 512, 0);
     };
     auto dma_phase = [&](int ph, int buf) {
 #pragma unroll
@@ -106,7 +96,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const AttnBwdArgs a,
         else { AQ_BARRIER_N(24); }
     };
     // identity B operand of the transposing MFMA: lane (n, g), k-slot 4g + t
-    half4q ident;
+    s3d_half4 ident;
 #pragma unroll
     for (int t = 0; t < 4; ++t) ident[t] = (4 * g + t == m) ? (_Float16)1.f : (_Float16)0.f;
 
@@ -129,11 +119,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const AttnBwdArgs a,
     for (long item = blockIdx.x; item < items; item += gridDim.x) {
         const long grp = item >> 1;
         const int q0 = 8 * (int)(item & 1) + 2 * wave;
-        half8q xl[2][4], xh[2][4];
+        s3d_half8 xl[2][4], xh[2][4];
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
-            for (int u = 0; u < 4; ++u) split8pk(xf[r][u][0], xf[r][u][1], xh[r][u], xl[r][u]);
+            for (int u = 0; u < 4; ++u) s3d_split8(xf[r][u][0], xf[r][u][1], xh[r][u], xl[r][u]);
         const bool more_items = item + gridDim.x < items;
 #pragma unroll 1
         for (int h = 0; h < 4; ++h) {
@@ -154,9 +144,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const AttnBwdArgs a,
                     const unsigned lq = lpar4 + (unsigned)h * 128u;
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        AQ_READ(bq[j], lq, 64 * j);
-                        AQ_READ(bk[j], lq, 512 + 64 * j);
-                        AQ_READ(bv[j], lq, 1024 + 64 * j);
+                        S3D_DS_READ(bq[j], lq, 64 * j);
+                        S3D_DS_READ(bk[j], lq, 512 + 64 * j);
+                        S3D_DS_READ(bv[j], lq, 1024 + 64 * j);
                     }
                 }
                 ring_barrier(h);   // this phase's fragments have landed; the slot of three phases ahead is free
@@ -165,12 +155,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const AttnBwdArgs a,
                 const int nbuf = (int)((ps + 3) & 3);
                 const unsigned lwa = lds_ring + (unsigned)(ps & 3) * (AQ3_SLOT_HALFS * 2);
                 f32x4 d[2][2], c0[2];
-                half8q fh[2][2], fl[2][2];
+                s3d_half8 fh[2][2], fl[2][2];
 #define AQB_STEP_READS(B, U)                                         \
-    AQ_READ(fh[B][0], lwa, (U) * 2048);                              \
-    AQ_READ(fl[B][0], lwa, (U) * 2048 + 1024);                       \
-    AQ_READ(fh[B][1], lwa, (4 + (U)) * 2048);                        \
-    AQ_READ(fl[B][1], lwa, (4 + (U)) * 2048 + 1024);
+    S3D_DS_READ(fh[B][0], lwa, (U) * 2048);                              \
+    S3D_DS_READ(fl[B][0], lwa, (U) * 2048 + 1024);                       \
+    S3D_DS_READ(fh[B][1], lwa, (4 + (U)) * 2048);                        \
+    S3D_DS_READ(fl[B][1], lwa, (4 + (U)) * 2048 + 1024);
 #define AQB_STEP_MFMA(B, U)                                                                                  \
     _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                          \
         if (j == 1) {                                                                                        \
@@ -178,25 +168,25 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const AttnBwdArgs a,
             dma_piece(nph, nbuf, U);                                                                         \
             __builtin_amdgcn_sched_barrier(0);                                                               \
         }                                                                                                    \
-        d[0][j] = mfma3q<SINGLE>(fh[B][j], fl[B][j], xh[0][U], xl[0][U], (U) == 0 ? c0[j] : d[0][j]);         \
-        d[1][j] = mfma3q<SINGLE>(fh[B][j], fl[B][j], xh[1][U], xl[1][U], (U) == 0 ? c0[j] : d[1][j]);         \
+        d[0][j] = s3d_mfma3<SINGLE>(fh[B][j], fl[B][j], xh[0][U], xl[0][U], (U) == 0 ? c0[j] : d[0][j]);     \
+        d[1][j] = s3d_mfma3<SINGLE>(fh[B][j], fl[B][j], xh[1][U], xl[1][U], (U) == 0 ? c0[j] : d[1][j]);     \
     }                                                                                                        \
     __builtin_amdgcn_sched_barrier(0);
                 AQB_STEP_READS(0, 0)
                 AQB_STEP_READS(1, 1)
-                AQ_WAIT4(4, fh[0][0], fl[0][0], fh[0][1], fl[0][1]);
+                S3D_LGKM_WAIT4(4, fh[0][0], fl[0][0], fh[0][1], fl[0][1]);
                 if (part == 0)   // the bias reads are older than the fragment reads: landed with this wait
                     asm volatile("" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bk[0]), "+v"(bk[1]), "+v"(bv[0]), "+v"(bv[1]));
 #pragma unroll
                 for (int j = 0; j < 2; ++j) c0[j] = part == 0 ? bq[j] : part == 1 ? bk[j] : bv[j];
                 AQB_STEP_MFMA(0, 0)
                 AQB_STEP_READS(0, 2)
-                AQ_WAIT4(4, fh[1][0], fl[1][0], fh[1][1], fl[1][1]);
+                S3D_LGKM_WAIT4(4, fh[1][0], fl[1][0], fh[1][1], fl[1][1]);
                 AQB_STEP_MFMA(1, 1)
                 AQB_STEP_READS(1, 3)
-                AQ_WAIT4(4, fh[0][0], fl[0][0], fh[0][1], fl[0][1]);
+                S3D_LGKM_WAIT4(4, fh[0][0], fl[0][0], fh[0][1], fl[0][1]);
                 AQB_STEP_MFMA(0, 2)
-                AQ_WAIT4(0, fh[1][0], fl[1][0], fh[1][1], fl[1][1]);
+                S3D_LGKM_WAIT4(0, fh[1][0], fl[1][0], fh[1][1], fl[1][1]);
                 AQB_STEP_MFMA(1, 3)
 #undef AQB_STEP_READS
 #undef AQB_STEP_MFMA
@@ -213,19 +203,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const AttnBwdArgs a,
             // =============== core backward, one query at a time ===============
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                half8q kh, kl, qsh, qsl, vh, vl, doh, dol;
-                half4q quh[2], qul[2];   // unscaled q tiles (the operand of dK)
-                split8pk(kd[r][0], kd[r][1], kh, kl);
-                split8pk(qd[r][0] * scale, qd[r][1] * scale, qsh, qsl);
-                split8pk(vd[r][0], vd[r][1], vh, vl);
-                split8pk(dod[r][0], dod[r][1], doh, dol);
-                split4pk(qd[r][0], quh[0], qul[0]);
-                split4pk(qd[r][1], quh[1], qul[1]);
-                AQB_SETTLE()
-                const f32x4 s = mfma3q<false>(kh, kl, qsh, qsl, zero4());      // S^T[key 4g+i][token m], log2 units
-                const f32x4 dp = mfma3q<false>(vh, vl, doh, dol, zero4());     // dPd^T[key][token]
+                s3d_half8 kh, kl, qsh, qsl, vh, vl, doh, dol;
+                s3d_half4 quh[2], qul[2];   // unscaled q tiles (the operand of dK)
+                s3d_split8(kd[r][0], kd[r][1], kh, kl);
+                s3d_split8(qd[r][0] * scale, qd[r][1] * scale, qsh, qsl);
+                s3d_split8(vd[r][0], vd[r][1], vh, vl);
+                s3d_split8(dod[r][0], dod[r][1], doh, dol);
+                s3d_split4(qd[r][0], quh[0], qul[0]);
+                s3d_split4(qd[r][1], quh[1], qul[1]);
+                S3D_SPLIT_SETTLE()
+                const f32x4 s = s3d_mfma3<false>(kh, kl, qsh, qsl, zero4());      // S^T[key 4g+i][token m], log2 units
+                const f32x4 dp = s3d_mfma3<false>(vh, vl, doh, dol, zero4());     // dPd^T[key][token]
                 // plain forms of K, Q, dO (lane = head dim, registers = tokens 4g+i): tile transposes of the halves
-                half4q kph[2], kpl[2], qph[2], qpl[2], dph[2], dpl[2];
+                s3d_half4 kph[2], kpl[2], qph[2], qpl[2], dph[2], dpl[2];
                 kph[0] = transpose16(lo4(kh), ident); kph[1] = transpose16(hi4(kh), ident);
                 kpl[0] = transpose16(lo4(kl), ident); kpl[1] = transpose16(hi4(kl), ident);
                 qph[0] = transpose16(quh[0], ident); qph[1] = transpose16(quh[1], ident);
@@ -240,14 +230,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const AttnBwdArgs a,
                     e[i] = (4 * g + i < T) ? s[i] : -1e30f;
                     mx = fmaxf(mx, e[i]);
                 }
-                mx = colmax16(mx);
+                mx = s3d_colmax16(mx);
                 float den = 0.f;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     e[i] = __builtin_amdgcn_exp2f(e[i] - mx);
                     den += e[i];
                 }
-                const float inv = __builtin_amdgcn_rcpf(colsum16(den));
+                const float inv = __builtin_amdgcn_rcpf(s3d_colsum16(den));
                 float mk[4] = {1.f, 1.f, 1.f, 1.f};
                 if (a.d0.p > 0.f) {
                     const unsigned long long rowq = (unsigned long long)((grp * T + mt) * S3D_GROUP + q0 + r);
@@ -260,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const AttnBwdArgs a,
                     dpm[i] = dp[i] * mk[i];
                     dot += p[i] * dpm[i];
                 }
-                dot = colsum16(dot);
+                dot = s3d_colsum16(dot);
                 const float colf = row_ok ? 1.f : 0.f;   // a padding query token contributes nothing to dK / dV
                 f32x4 ds, pd;
 #pragma unroll
@@ -268,19 +258,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const AttnBwdArgs a,
                     ds[i] = p[i] * (dpm[i] - dot) * (scale0 * colf);
                     pd[i] = p[i] * mk[i] * colf;
                 }
-                half4q dsh, dsl, pdh, pdl;
-                split4pk(ds, dsh, dsl);
-                split4pk(pd, pdh, pdl);
-                AQB_SETTLE()
+                s3d_half4 dsh, dsl, pdh, pdl;
+                s3d_split4(ds, dsh, dsl);
+                s3d_split4(pd, pdh, pdl);
+                S3D_SPLIT_SETTLE()
                 // token-transposed dS and Pd: lane (key, g), registers = query tokens 4g+i
-                const half4q dth = transpose16(dsh, ident), dtl = transpose16(dsl, ident);
-                const half4q pth = transpose16(pdh, ident), ptl = transpose16(pdl, ident);
+                const s3d_half4 dth = transpose16(dsh, ident), dtl = transpose16(dsl, ident);
+                const s3d_half4 pth = transpose16(pdh, ident), ptl = transpose16(pdl, ident);
                 f32x4 dq[2], dk[2], dv[2];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    dq[j] = mfma3h<false>(kph[j], kpl[j], dsh, dsl, zero4());   // dQ^T[dim][token]
-                    dk[j] = mfma3h<false>(qph[j], qpl[j], dth, dtl, zero4());   // dK^T[dim][key]
-                    dv[j] = mfma3h<false>(dph[j], dpl[j], pth, ptl, zero4());   // dV^T[dim][key]
+                    dq[j] = s3d_mfma3_k16<false>(kph[j], kpl[j], dsh, dsl, zero4());   // dQ^T[dim][token]
+                    dk[j] = s3d_mfma3_k16<false>(qph[j], qpl[j], dth, dtl, zero4());   // dK^T[dim][key]
+                    dv[j] = s3d_mfma3_k16<false>(dph[j], dpl[j], pth, ptl, zero4());   // dV^T[dim][key]
                 }
                 // rows leave as full 128-byte lines: lane m < 8 carries dims 0-15, lane m >= 8 dims 16-31 of token m & 7 (+ 8)
                 float* ob = a.dQKV + ((grp * T + (m & 7)) * S3D_GROUP + q0 + r) * 384 + 32 * h + 16 * (m >> 3) + 4 * g;
