@@ -148,9 +148,13 @@ struct PackedConv {
     size_t w16;              // split-precision (f16 hi/lo) image, same size as w
     int cout_pad, KU;
 };
-struct UNetLayout {
+// the VGG16-BN encoder's weights: the start of both the U-Net's packed image and the GT encoder's (api_gt.inc)
+struct EncLayout {
     PackedConv enc[13];
     size_t pool_scale[4], pool_shift[4];  // BN that follows tap convs 1,3,6,9 (applied by the pool kernel)
+};
+struct UNetLayout {
+    EncLayout E;
     PackedConv trans_c, trans_up[4], up_t[4], up_c1[4], up_c2[4], outc;
     size_t emds;
     size_t enc0_raw;   // conv1_1's weight as is, (64,3,3,3): the 3-channel first layer runs a direct fp32 kernel on the NCHW image
@@ -159,40 +163,51 @@ struct UNetLayout {
 
 static int pad16(int c) { return (c + 15) / 16 * 16; }
 
-static UNetLayout unet_layout(int n_slices) {
-    UNetLayout L;
+// float offsets of the pieces of a packed weight image, each 16-byte aligned
+struct ImageAlloc {
     size_t off = 0;
-    auto take = [&](size_t n) {
+    size_t take(size_t n) {
         size_t o = off;
         off += (n + 3) / 4 * 4;
         return o;
-    };
-    auto conv = [&](PackedConv& pc, int cout_pad, int KU) {
+    }
+    void conv(PackedConv& pc, int cout_pad, int KU) {
         pc.cout_pad = cout_pad;
         pc.KU = KU;
         pc.w = take((size_t)cout_pad * KU * 16);
         pc.w16 = take((size_t)cout_pad * KU * 16);
         pc.scale = take(cout_pad);
         pc.shift = take(cout_pad);
-    };
-    for (int i = 0; i < 13; ++i) conv(L.enc[i], kEncCout[i], 9 * pad16(kEncCin[i]) / 16);
+    }
+};
+
+static EncLayout enc_layout(ImageAlloc& a) {
+    EncLayout E;
+    for (int i = 0; i < 13; ++i) a.conv(E.enc[i], kEncCout[i], 9 * pad16(kEncCin[i]) / 16);
     const int tapc[4] = {64, 128, 256, 512};
     for (int i = 0; i < 4; ++i) {
-        L.pool_scale[i] = take(tapc[i]);
-        L.pool_shift[i] = take(tapc[i]);
+        E.pool_scale[i] = a.take(tapc[i]);
+        E.pool_shift[i] = a.take(tapc[i]);
     }
-    conv(L.trans_c, 512, 640 / 16);
+    return E;
+}
+
+static UNetLayout unet_layout(int n_slices) {
+    UNetLayout L;
+    ImageAlloc a;
+    L.E = enc_layout(a);
+    a.conv(L.trans_c, 512, 640 / 16);
     for (int i = 0; i < 4; ++i) {
         const int C = kUpC[i], Ct = C / 2;
-        conv(L.trans_up[i], Ct, C / 16);
-        conv(L.up_t[i], 4 * Ct, C / 16);
-        conv(L.up_c1[i], Ct, 2 * 9 * Ct / 16);
-        conv(L.up_c2[i], Ct, 9 * Ct / 16);
+        a.conv(L.trans_up[i], Ct, C / 16);
+        a.conv(L.up_t[i], 4 * Ct, C / 16);
+        a.conv(L.up_c1[i], Ct, 2 * 9 * Ct / 16);
+        a.conv(L.up_c2[i], Ct, 9 * Ct / 16);
     }
-    conv(L.outc, 16, 32 / 16);
-    L.emds = take((size_t)n_slices * 128);
-    L.enc0_raw = take(64 * 27);
-    L.total = off;
+    a.conv(L.outc, 16, 32 / 16);
+    L.emds = a.take((size_t)n_slices * 128);
+    L.enc0_raw = a.take(64 * 27);
+    L.total = a.off;
     return L;
 }
 
@@ -221,6 +236,26 @@ static int pack_linear(const float* w, float* dst, int n, int n_pad, int k, int 
     return launch_pack(a, st);
 }
 
+static int pack_encoder(const S3dConvParams P[13], float* base, const EncLayout& E, hipStream_t st) {
+    for (int i = 0; i < 13; ++i) {
+        const PackedConv& pc = E.enc[i];
+        TRY(pack_conv3(P[i].w, base + pc.w, kEncCout[i], pc.cout_pad, kEncCin[i], 0, kEncCin[i], pc.KU, 0, 9, st));
+        if (kEncCin[i] % 32 == 0)
+            TRY(pack_conv3(P[i].w, base + pc.w16, kEncCout[i], pc.cout_pad, kEncCin[i], 0, kEncCin[i], pc.KU, 0, 9, st, 1));
+        // a tap's raw conv output is the skip tensor / feature level: bias only (SURVEY 8(a) a-2, vgg16bn_feats.py:33-38);
+        // its BatchNorm is applied by the pool kernel that opens the next block
+        if (kEncTap[i])
+            TRY(launch_fold_bn(P[i].b, nullptr, base + pc.scale, base + pc.shift, kEncCout[i], pc.cout_pad, 1, 0, st));
+        else
+            TRY(launch_fold_bn(P[i].b, P[i].bn, base + pc.scale, base + pc.shift, kEncCout[i], pc.cout_pad, 1, 1, st));
+    }
+    const int tapi[4] = {1, 3, 6, 9};
+    for (int i = 0; i < 4; ++i)
+        TRY(launch_fold_bn(nullptr, P[tapi[i]].bn, base + E.pool_scale[i], base + E.pool_shift[i], kEncCout[tapi[i]],
+                           kEncCout[tapi[i]], 1, 0, st));
+    return 0;
+}
+
 extern "C" int s3d_unet_pack(const S3dUNetParams* P, void* packed, size_t packed_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     S3D_CHECK_ARG(P && packed, "unet_pack: null argument");
@@ -231,28 +266,11 @@ extern "C" int s3d_unet_pack(const S3dUNetParams* P, void* packed, size_t packed
         return S3D_E_WORKSPACE;
     }
     float* base = (float*)packed;
-    for (int i = 0; i < 13; ++i) {
-        const PackedConv& pc = L.enc[i];
-        TRY(pack_conv3(P->enc[i].w, base + pc.w, kEncCout[i], pc.cout_pad, kEncCin[i], 0, kEncCin[i], pc.KU, 0, 9,
-                       st));
-        if (kEncCin[i] % 32 == 0)
-            TRY(pack_conv3(P->enc[i].w, base + pc.w16, kEncCout[i], pc.cout_pad, kEncCin[i], 0, kEncCin[i], pc.KU, 0,
-                           9, st, 1));
-        if (kEncTap[i])  // raw conv output is the skip tensor: bias only
-            TRY(launch_fold_bn(P->enc[i].b, nullptr, base + pc.scale, base + pc.shift, kEncCout[i], pc.cout_pad, 1,
-                               0, st));
-        else
-            TRY(launch_fold_bn(P->enc[i].b, P->enc[i].bn, base + pc.scale, base + pc.shift, kEncCout[i],
-                               pc.cout_pad, 1, 1, st));
-    }
+    TRY(pack_encoder(P->enc, base, L.E, st));
     if (hipMemcpyAsync(base + L.enc0_raw, P->enc[0].w, 64 * 27 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
         s3d_set_error("unet_pack: copy of conv1_1's weight failed");
         return S3D_E_ARG;
     }
-    const int tapi[4] = {1, 3, 6, 9};
-    for (int i = 0; i < 4; ++i)
-        TRY(launch_fold_bn(nullptr, P->enc[tapi[i]].bn, base + L.pool_scale[i], base + L.pool_shift[i],
-                           kEncCout[tapi[i]], kEncCout[tapi[i]], 1, 0, st));
     TRY(pack_linear(P->trans_c.w, base + L.trans_c.w, 512, 512, 640, 640, 0, st));
     TRY(pack_linear(P->trans_c.w, base + L.trans_c.w16, 512, 512, 640, 640, 0, st, 1));
     TRY(launch_fold_bn(P->trans_c.b, nullptr, base + L.trans_c.scale, base + L.trans_c.shift, 512, 512, 1, 0, st));
@@ -329,11 +347,11 @@ extern "C" size_t s3d_unet_workspace_bytes(int batch, int size, int n_slices) {
     return unet_ws(batch, size, n_slices).total * sizeof(float);
 }
 
-static int g_desc_prec = S3D_PREC_F32;   // set by the entry point that builds descriptors (host, single stream)
-static ConvLaunch conv_desc(const float* base, const PackedConv& pc, int N, int H, int W, int ks, int act) {
+// prec: S3D_PREC_F32, F16X3 or F16 (the split-precision image is used when the layer allows it)
+static ConvLaunch conv_desc(const float* base, const PackedConv& pc, int prec, int N, int H, int W, int ks, int act) {
     ConvLaunch c = {};
-    c.wpk16 = g_desc_prec != S3D_PREC_F32 ? (const void*)(base + pc.w16) : nullptr;
-    c.single_pass = g_desc_prec == S3D_PREC_F16;
+    c.wpk16 = prec != S3D_PREC_F32 ? (const void*)(base + pc.w16) : nullptr;
+    c.single_pass = prec == S3D_PREC_F16;
     c.N = N; c.H = H; c.W = W; c.ks = ks;
     c.CoutPad = pc.cout_pad; c.wpk = base + pc.w; c.KU = pc.KU;
     c.scale = base + pc.scale; c.shift = base + pc.shift;
@@ -342,6 +360,54 @@ static ConvLaunch conv_desc(const float* base, const PackedConv& pc, int N, int 
 }
 static ConvSrc plain_src(const float* p, int C) { return ConvSrc{p, C, 1, 0, 0}; }
 
+// 1x1 convolution of x (k channels; N images of H x W pixels, or one 1 x nrows image of rows) onto n channels: the
+// projections to 128 channels and the row-linear maps.  Epilogue: + shift (a bias, or none), then act.  w16: the
+// split-precision image, or nullptr for fp32; single: one f16 product per MFMA (S3D_PREC_F16).
+static ConvLaunch proj_desc(const float* w, const void* w16, bool single, int n, int k, const float* x, int N, int H,
+                            int W, float* out, const float* shift = nullptr, int act = S3D_ACT_NONE) {
+    ConvLaunch c = {};
+    c.N = N; c.H = H; c.W = W; c.ks = 1;
+    c.CoutPad = n; c.wpk = w; c.KU = k / 16;
+    c.wpk16 = w16; c.single_pass = single;
+    c.shift = shift; c.act = act;
+    c.out_mode = S3D_OUT_NHWC; c.cout_store = n; c.out_cstride = n;
+    c.nsrc = 1;
+    c.src[0] = plain_src(x, k);
+    c.out = out;
+    return c;
+}
+
+// VGG16-BN encoder (unet_custom.py:43-47, vgg16bn_feats.py:42-57) on N images of S x S, from conv `first` on: `in` is
+// that conv's input (first = 0: the 16-channel NHWC image; first = 1: conv1_1's output, in pp[0]).  The other outputs
+// ping-pong through pp; tap k's raw output goes to tap[k], and taps 0-3 are followed by BN + ReLU + max-pool into pool[k].
+static int encoder_fwd(const float* base, const EncLayout& E, int prec, int N, int S, int first, const float* in,
+                       float* const tap[5], float* const pp[2], float* const pool[4], float* splitk, hipStream_t st) {
+    const float* cur = in;
+    int curC = first ? kEncCout[0] : 16, res = S, tap_i = 0, flip = first;
+    for (int i = first; i < 13; ++i) {
+        ConvLaunch c = conv_desc(base, E.enc[i], prec, N, res, res, 3, kEncTap[i] ? S3D_ACT_NONE : S3D_ACT_RELU);
+        c.nsrc = 1;
+        c.src[0] = plain_src(cur, curC);
+        c.splitk_ws = splitk; c.splitk_floats = S3D_SPLITK_FLOATS;
+        c.out = kEncTap[i] ? tap[tap_i] : pp[flip];
+        TRY(launch_conv(c, st));
+        cur = c.out;
+        curC = kEncCout[i];
+        if (!kEncTap[i]) {
+            flip ^= 1;
+            continue;
+        }
+        if (tap_i < 4) {  // BN + ReLU + MaxPool open the next block
+            TRY(launch_bn_relu_pool(tap[tap_i], base + E.pool_scale[tap_i], base + E.pool_shift[tap_i], pool[tap_i], N,
+                                    res, res, curC, st));
+            cur = pool[tap_i];
+            res /= 2;
+        }
+        ++tap_i;
+    }
+    return 0;
+}
+
 extern "C" int s3d_unet_encode_fwd(const void* packed, const float* img, const S3dPyramid* out,
                                    float* slices_rec, int B, int S, int ns, int prec, void* workspace,
                                    size_t workspace_bytes, void* stream) {
@@ -349,7 +415,6 @@ extern "C" int s3d_unet_encode_fwd(const void* packed, const float* img, const S
     S3D_CHECK_ARG(prec == S3D_PREC_F32 || prec == S3D_PREC_F16X3 || prec == S3D_PREC_F16 || prec == S3D_PREC_BF16,
                   "unet_encode: precision mode %d", prec);
     if (prec == S3D_PREC_BF16) prec = S3D_PREC_F16;   // the bf16 mode covers the decoder's attention / FFN GEMMs; the conv engine runs single-pass f16
-    struct PrecScope { PrecScope(int p) { g_desc_prec = p; } ~PrecScope() { g_desc_prec = S3D_PREC_F32; } } ps_(prec);
     S3D_CHECK_ARG(packed && img && out && workspace, "unet_encode: null argument");
     S3D_CHECK_ARG(B >= 1 && S >= 16 && S % 16 == 0, "unet_encode: B=%d S=%d (S must be a multiple of 16)", B, S);
     S3D_CHECK_ARG(ns >= 1 && ns <= 12, "unet_encode: n_slices %d", ns);
@@ -365,44 +430,18 @@ extern "C" int s3d_unet_encode_fwd(const void* packed, const float* img, const S
 
     ProfScope prof_(S3D_PROF_UNET, st);
     // ---- VGG16-BN encoder (unet_custom.py:43-47) ----
-    const float* cur = ws + W.in16;
-    int curC = 16, res = S, tap_i = 0;
-    float* pp[2] = {ws + W.a, ws + W.b};
-    int flip = 0;
-    for (int i = 0; i < 13; ++i) {
-        if (i == 0) {   // 3 -> 64 straight from the NCHW image: a direct fp32 kernel bound by its 64-channel write
-                        // (the padded implicit GEMM spent 100 us on 0.9 GFLOP); folded BN + ReLU in its epilogue
-            TRY(launch_conv3x3_first(img, 3, base + L.enc0_raw, nullptr, pp[flip], B, S, S, st, base + L.enc[0].scale,
-                                     base + L.enc[0].shift, 1));
-            cur = pp[flip];
-            curC = kEncCout[0];
-            flip ^= 1;
-            continue;
-        }
-        ConvLaunch c = conv_desc(base, L.enc[i], B, res, res, 3, kEncTap[i] ? S3D_ACT_NONE : S3D_ACT_RELU);
-        c.nsrc = 1;
-        c.src[0] = plain_src(cur, curC);
-        c.splitk_ws = ws + W.splitk; c.splitk_floats = S3D_SPLITK_FLOATS;
-        float* dst = kEncTap[i] ? ws + W.x[tap_i] : pp[flip];
-        c.out = dst;
-        TRY(launch_conv(c, st));
-        cur = dst;
-        curC = kEncCout[i];
-        if (!kEncTap[i]) flip ^= 1;
-        if (kEncTap[i]) {
-            if (tap_i < 4) {  // BN + ReLU + MaxPool open the next block
-                TRY(launch_bn_relu_pool(ws + W.x[tap_i], base + L.pool_scale[tap_i], base + L.pool_shift[tap_i],
-                                        ws + W.p[tap_i], B, res, res, curC, st));
-                cur = ws + W.p[tap_i];
-                res /= 2;
-            }
-            ++tap_i;
-        }
-    }
+    // conv1_1, 3 -> 64 straight from the NCHW image: a direct fp32 kernel bound by its 64-channel write (the padded
+    // implicit GEMM spent 100 us on 0.9 GFLOP); folded BN + ReLU in its epilogue
+    float* const pp[2] = {ws + W.a, ws + W.b};
+    float* const tap[5] = {ws + W.x[0], ws + W.x[1], ws + W.x[2], ws + W.x[3], ws + W.x[4]};
+    float* const pool[4] = {ws + W.p[0], ws + W.p[1], ws + W.p[2], ws + W.p[3]};
+    TRY(launch_conv3x3_first(img, 3, base + L.enc0_raw, nullptr, pp[0], B, S, S, st, base + L.E.enc[0].scale,
+                             base + L.E.enc[0].shift, 1));
+    TRY(encoder_fwd(base, L.E, prec, B, S, 1, pp[0], tap, pp, pool, ws + W.splitk, st));
     // ---- latent = trans_c(cat[tile(x5), emb])  (unet_custom.py:50-58) ----
     const int r5 = S / 16;
     {
-        ConvLaunch c = conv_desc(base, L.trans_c, B * ns, r5, r5, 1, S3D_ACT_NONE);
+        ConvLaunch c = conv_desc(base, L.trans_c, prec, B * ns, r5, r5, 1, S3D_ACT_NONE);
         c.nsrc = 2;
         c.src[0] = ConvSrc{ws + W.x[4], 512, ns, 0, 0};
         c.src[1] = ConvSrc{base + L.emds, 128, 1, ns, 1};
@@ -415,14 +454,14 @@ extern "C" int s3d_unet_encode_fwd(const void* packed, const float* img, const S
     for (int i = 0; i < 4; ++i) {
         const int C = kUpC[i], Ct = C / 2, ro = rp * 2;
         {  // skip projection, once per image: trans_up(expand_bs(x)) == expand_bs(trans_up(x))
-            ConvLaunch c = conv_desc(base, L.trans_up[i], B, ro, ro, 1, S3D_ACT_NONE);
+            ConvLaunch c = conv_desc(base, L.trans_up[i], prec, B, ro, ro, 1, S3D_ACT_NONE);
             c.nsrc = 1;
             c.src[0] = plain_src(ws + W.x[3 - i], C);
             c.out = ws + W.proj;
             TRY(launch_conv(c, st));
         }
         {  // ConvTranspose2d 2x2 s2 as a 1x1 GEMM with N = 4*Ct and a quadrant-scatter store
-            ConvLaunch c = conv_desc(base, L.up_t[i], B * ns, rp, rp, 1, S3D_ACT_NONE);
+            ConvLaunch c = conv_desc(base, L.up_t[i], prec, B * ns, rp, rp, 1, S3D_ACT_NONE);
             c.nsrc = 1;
             c.src[0] = plain_src(prev, C);
             c.out = ws + W.up;
@@ -431,7 +470,7 @@ extern "C" int s3d_unet_encode_fwd(const void* packed, const float* img, const S
             TRY(launch_conv(c, st));
         }
         {
-            ConvLaunch c = conv_desc(base, L.up_c1[i], B * ns, ro, ro, 3, S3D_ACT_RELU);
+            ConvLaunch c = conv_desc(base, L.up_c1[i], prec, B * ns, ro, ro, 3, S3D_ACT_RELU);
             c.nsrc = 2;
             c.src[0] = ConvSrc{ws + W.proj, Ct, ns, 0, 0};
             c.src[1] = plain_src(ws + W.up, Ct);
@@ -439,7 +478,7 @@ extern "C" int s3d_unet_encode_fwd(const void* packed, const float* img, const S
             TRY(launch_conv(c, st));
         }
         {
-            ConvLaunch c = conv_desc(base, L.up_c2[i], B * ns, ro, ro, 3, S3D_ACT_RELU);
+            ConvLaunch c = conv_desc(base, L.up_c2[i], prec, B * ns, ro, ro, 3, S3D_ACT_RELU);
             c.nsrc = 1;
             c.src[0] = plain_src(ws + W.mid, Ct);
             c.out = out->level[i + 1];
@@ -449,7 +488,7 @@ extern "C" int s3d_unet_encode_fwd(const void* packed, const float* img, const S
         rp = ro;
     }
     if (slices_rec) {  // OutConv 1x1 + tanh -> NCHW (unet_parts.py:78-84)
-        ConvLaunch c = conv_desc(base, L.outc, B * ns, S, S, 1, S3D_ACT_TANH);
+        ConvLaunch c = conv_desc(base, L.outc, prec, B * ns, S, S, 1, S3D_ACT_TANH);
         c.nsrc = 1;
         c.src[0] = plain_src(prev, 32);
         c.out = slices_rec;
@@ -562,7 +601,7 @@ extern "C" int s3d_vgg_loss_fwd(const void* packed, const float* pred, const flo
     int curC = 16, res = S, flip = 0;
     float* pp[2] = {ws + W.a, ws + W.b};
     for (int i = 0; i < 14; ++i) {
-        ConvLaunch c = conv_desc(base, L.conv[i], N2, res, res, 3, i == 13 ? S3D_ACT_NONE : S3D_ACT_RELU);
+        ConvLaunch c = conv_desc(base, L.conv[i], S3D_PREC_F32, N2, res, res, 3, i == 13 ? S3D_ACT_NONE : S3D_ACT_RELU);
         c.nsrc = 1;
         c.src[0] = plain_src(cur, curC);
         c.out = pp[flip];
@@ -719,19 +758,11 @@ extern "C" int s3d_latent_build(const void* head_packed, const S3dPyramid* pyr, 
     if (prec == S3D_PREC_BF16) prec = S3D_PREC_F16;   // (see s3d_unet_encode_fwd)
     ProfScope prof_(S3D_PROF_LATENT, st);
     const int lc[3] = {512, 256, 128};
-    for (int l = 0; l < 3; ++l) {
+    for (int l = 0; l < 3; ++l) {   // identity epilogue: fc_s bias is added by the sampler
         const int r = (pyr->size / 16) << l;
-        ConvLaunch c = {};
-        c.N = pyr->n_img; c.H = r; c.W = r; c.ks = 1;
-        c.CoutPad = 128; c.wpk = b + H.wproj[l]; c.KU = lc[l] / 16;
-        c.wpk16 = prec != S3D_PREC_F32 ? (const void*)(b + H.wproj16[l]) : nullptr;
-        c.single_pass = prec == S3D_PREC_F16;
-        c.scale = nullptr; c.shift = nullptr;  // identity epilogue: fc_s bias is added by the sampler
-        c.act = S3D_ACT_NONE; c.out_mode = S3D_OUT_NHWC; c.cout_store = 128; c.out_cstride = 128;
-        c.nsrc = 1;
-        c.src[0] = plain_src(pyr->level[l], lc[l]);
-        c.out = out->proj[l];
-        TRY(launch_conv(c, st));
+        TRY(launch_conv(proj_desc(b + H.wproj[l], prec != S3D_PREC_F32 ? b + H.wproj16[l] : nullptr,
+                                  prec == S3D_PREC_F16, 128, lc[l], pyr->level[l], pyr->n_img, r, r, out->proj[l]),
+                        st));
     }
     return 0;
 }
@@ -749,20 +780,23 @@ extern "C" int s3d_latent_build(const void* head_packed, const S3dPyramid* pyr, 
 #define S3D_FFN_LAUNCH_GROUPS 16384
 
 struct DecodeWs {
-    size_t X, X0, perm, sortws, last, total;
+    size_t X1, X, X0, perm, sortws, last, total;
     long chunk;   // groups per pass
 };
 // scratch of the absorbed last-layer attention per query row: x0 | u (128 each), qt | xbar (512 each)
 #define S3D_LAST_ROW_FLOATS (2 * 128 + 2 * 512)
 #define S3D_SORT_MIN_QUERIES 4096   // below this the sort costs more than the locality buys
-static DecodeWs decode_ws(int batch, long n_qry, int ns, long chunk_groups = S3D_CHUNK_GROUPS) {
+// x1: one more token tensor X1 in front of X (the GT decoder's sampled tokens, before fc_local[2])
+static DecodeWs decode_ws(int batch, long n_qry, int ns, long chunk_groups, bool x1 = false) {
     const long gpb = (n_qry + S3D_GROUP - 1) / S3D_GROUP;
     long g = gpb * batch;
     if (g > chunk_groups) g = chunk_groups;
+    const size_t tokens = (size_t)g * (ns + 1) * S3D_GROUP * 128;
     DecodeWs W;
     W.chunk = chunk_groups;
-    W.X = 0;
-    W.X0 = (size_t)g * (ns + 1) * S3D_GROUP * 128;
+    W.X1 = 0;
+    W.X = x1 ? tokens : 0;
+    W.X0 = W.X + tokens;
     W.perm = W.X0 + (size_t)g * S3D_GROUP * 128;
     W.sortws = W.perm + (size_t)batch * n_qry;
     W.last = (W.sortws + query_sort_ws_ints(batch, n_qry) + 63) / 64 * 64;
@@ -780,7 +814,7 @@ static bool decode_ws_fit(int batch, long n_qry, int ns, size_t bytes, DecodeWs&
 }
 
 extern "C" size_t s3d_decode_workspace_bytes(int batch, long n_qry, int n_slices) {
-    return decode_ws(batch, n_qry, n_slices).total * sizeof(float);
+    return decode_ws(batch, n_qry, n_slices, S3D_CHUNK_GROUPS).total * sizeof(float);
 }
 extern "C" size_t s3d_decode_workspace_bytes_min(int batch, long n_qry, int n_slices) {
     return decode_ws(batch, n_qry, n_slices, S3D_CHUNK_GROUPS_MIN).total * sizeof(float);
@@ -865,17 +899,10 @@ static LayerPtrs layer_ptrs(const float* b, const HeadLayout& H, int l) {
 
 // rows x k  ->  rows x n  linear map on the conv engine (1x1 convolution over a row "image")
 static int rows_linear(const float* b, size_t w32, size_t w16, int n, int k, const float* bias, const float* x,
-                       long nrows, float* out, const float* residual, int prec, hipStream_t st) {
-    ConvLaunch c = {};
-    c.N = 1; c.H = 1; c.W = (int)nrows; c.ks = 1;
-    c.CoutPad = n; c.wpk = b + w32; c.KU = k / 16;
-    c.wpk16 = prec != S3D_PREC_F32 ? (const void*)(b + w16) : nullptr;
-        c.single_pass = prec == S3D_PREC_F16;
-    c.shift = bias; c.act = S3D_ACT_NONE;
-    c.out_mode = S3D_OUT_NHWC; c.cout_store = n; c.out_cstride = n;
-    c.nsrc = 1;
-    c.src[0] = plain_src(x, k);
-    c.out = out; c.residual = residual;
+                       long nrows, float* out, const float* residual, int prec, hipStream_t st, int act = S3D_ACT_NONE) {
+    ConvLaunch c = proj_desc(b + w32, prec != S3D_PREC_F32 ? b + w16 : nullptr, prec == S3D_PREC_F16, n, k, x, 1, 1,
+                             (int)nrows, out, bias, act);
+    c.residual = residual;
     return launch_conv(c, st);
 }
 
@@ -930,6 +957,74 @@ static int attn_last_layer(const float* b, const HeadLayout& H, const LayerPtrs&
     return fold_ln ? 0 : launch_ln_fwd(u, lp.ln1g, lp.ln1b, X0, rows0, st);
 }
 
+// The three encoder layers + fc_out of one decode pass, shared by the Reg and GT decoders: X is the pass's token
+// tensor [gc][T][16][128], X0 / last its token-0 rows and the absorbed last layer's scratch, g0 its first group.
+// fold_ln: LayerNorm1 of the last layer in the final FFN kernel's prologue; bf16: attention + FFN GEMMs on the bf16
+// MFMA; stages: the capture of s3d_decode_points_stages_fwd (one pass over every group, one lane) or nullptr.
+struct DecodeStack {
+    const float* b;
+    const HeadLayout& H;
+    float *X, *X0, *last;
+    int T, prec;
+    bool fold_ln, bf16;
+    long gpb, n_qry, g0;
+    float* out;
+    float sign;
+    const int* perm;
+    float* stages;
+};
+// groups [gs, gs + gn) of the pass, enqueued on stream s; after_first_attn (optional) is recorded after the first attention
+static int decode_layers(const DecodeStack& D, hipStream_t s, long gs, long gn, hipEvent_t after_first_attn = nullptr) {
+    const int T = D.T, prec = D.prec, ffn_prec = D.bf16 ? S3D_PREC_BF16 : prec;
+    float* Xs = D.X + (size_t)gs * T * S3D_GROUP * 128;
+    float* X0s = D.X0 + (size_t)gs * S3D_GROUP * 128;
+    float* lasts = D.last + (size_t)gs * S3D_GROUP * S3D_LAST_ROW_FLOATS;
+    const size_t rows0 = (size_t)gn * S3D_GROUP * 128;   // with stages: token 0 after layer l at stages + (T + l) * rows0
+    for (int l = 0; l < S3D_N_LAYERS; ++l) {
+        const LayerPtrs lp = layer_ptrs(D.b, D.H, l);
+        const bool last = l == S3D_N_LAYERS - 1;
+        {
+            ProfScope prof_(S3D_PROF_ATTN, s);
+            if (last)          // only token 0 of the last layer is consumed (models.py:83): absorbed form, every mode
+                TRY(attn_last_layer(D.b, D.H, lp, Xs, X0s, gn, T, lasts, prec, s, D.fold_ln));
+            else if (prec != S3D_PREC_F32)
+                TRY(launch_attn_layer_q(Xs, gn, T, lp, s, prec == S3D_PREC_F16, D.bf16));
+            else
+                TRY(launch_attn_layer(Xs, nullptr, gn, T, lp, s));
+        }
+        if (l == 0 && after_first_attn && hipEventRecord(after_first_attn, s) != hipSuccess) {
+            s3d_set_error("decode: hipEventRecord failed");
+            return (int)hipErrorUnknown;
+        }
+        float* d = D.stages ? D.stages + (T + l) * rows0 : nullptr;
+        if (!last) {
+            for (long f0 = 0; f0 < gn; f0 += S3D_FFN_LAUNCH_GROUPS) {   // (rows are independent: any split is the same result)
+                const long fc = gn - f0 < S3D_FFN_LAUNCH_GROUPS ? gn - f0 : S3D_FFN_LAUNCH_GROUPS;
+                ProfScope prof_(S3D_PROF_FFN, s);
+                TRY(launch_ffn_layer(Xs + (size_t)f0 * T * S3D_GROUP * 128, fc * T * S3D_GROUP, lp, nullptr, nullptr, nullptr,
+                                     1.f, D.gpb, D.n_qry, D.g0 + gs + f0, ffn_prec, nullptr, s));
+            }
+            if (d) TRY(launch_tok0_copy(Xs, d, gn, T, 0, 128, s));
+        } else {
+            ProfScope prof_(S3D_PROF_FFN_FINAL, s);
+            if (d) {   // the final kernel keeps the layer's output rows in registers (LayerNorm -> fc_out): the capture
+                       // runs the full-row form of the same kernel on a copy of the token-0 rows
+                if (D.fold_ln) {   // X0 holds the pre-LayerNorm sums (the final kernel normalises them itself): the capture's copy is normalised here
+                    TRY(launch_ln_fwd(X0s, lp.ln1g, lp.ln1b, d, gn * S3D_GROUP, s));
+                } else if (hipMemcpyAsync(d, X0s, rows0 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
+                    s3d_set_error("decode stages: memcpy failed");
+                    return (int)hipErrorUnknown;
+                }
+                TRY(launch_ffn_layer(d, gn * S3D_GROUP, lp, nullptr, nullptr, nullptr, 1.f, D.gpb, D.n_qry, D.g0 + gs,
+                                     ffn_prec, nullptr, s));
+            }
+            TRY(launch_ffn_layer(X0s, gn * S3D_GROUP, lp, D.b + D.H.fco_w, D.b + D.H.fco_b, D.out, D.sign, D.gpb, D.n_qry,
+                                 D.g0 + gs, ffn_prec, D.perm, s, D.fold_ln));
+        }
+    }
+    return 0;
+}
+
 static int decode_impl(const void* head_packed, const S3dLatent* lat, const float* qry, const float* rot,
                        const float* trans, int flip_yz, int nx, float box, float sign, float* out, int batch,
                        long n_qry, int ns, int prec, void* workspace, size_t workspace_bytes, hipStream_t st,
@@ -942,7 +1037,6 @@ static int decode_impl(const void* head_packed, const S3dLatent* lat, const floa
                   "decode: precision mode %d not built", prec);
     const bool bf16 = prec == S3D_PREC_BF16;   // attention + FFN GEMMs on the bf16 MFMA; everything else as S3D_PREC_F16
     if (bf16) prec = S3D_PREC_F16;
-    const int ffn_prec = bf16 ? S3D_PREC_BF16 : prec;
     DecodeWs W;
     if (!decode_ws_fit(batch, n_qry, ns, workspace_bytes, W)) {
         s3d_set_error("decode: workspace %zu < %zu bytes (s3d_decode_workspace_bytes_min)", workspace_bytes, W.total * sizeof(float));
@@ -952,7 +1046,6 @@ static int decode_impl(const void* head_packed, const S3dLatent* lat, const floa
     const HeadLayout H = head_layout();
     const float* b = (const float*)head_packed;
     float* X = (float*)workspace + W.X;
-    float* X0 = (float*)workspace + W.X0;
     const int T = ns + 1;
     const long gpb = (n_qry + S3D_GROUP - 1) / S3D_GROUP;
     const long G = gpb * batch;
@@ -966,7 +1059,8 @@ static int decode_impl(const void* head_packed, const S3dLatent* lat, const floa
     // stage capture (s3d_decode_points_stages_fwd): one pass, queries in caller order
     S3D_CHECK_ARG(!stages || (G <= CHUNK && !perm), "decode stages: at most %d unsorted queries per object",
                   (int)S3D_SORT_MIN_QUERIES - 1);
-    const size_t rows_all = (size_t)G * T * S3D_GROUP * 128, rows0_all = (size_t)G * S3D_GROUP * 128;
+    DecodeStack D{b, H, X, (float*)workspace + W.X0, (float*)workspace + W.last, T, prec, prec != S3D_PREC_F32, bf16,
+                  gpb, n_qry, 0, out, sign, perm, stages};
     for (long g0 = 0; g0 < G; g0 += CHUNK) {
         const long gc = G - g0 < CHUNK ? G - g0 : CHUNK;
         SampleArgs sa = {};
@@ -983,60 +1077,12 @@ static int decode_impl(const void* head_packed, const S3dLatent* lat, const floa
             ProfScope prof_(S3D_PROF_SAMPLE, st);
             TRY(launch_sample_tokens(sa, st));
         }
-        if (stages && hipMemcpyAsync(stages, X, rows_all * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        if (stages && hipMemcpyAsync(stages, X, (size_t)G * T * S3D_GROUP * 128 * sizeof(float), hipMemcpyDeviceToDevice,
+                                     st) != hipSuccess) {
             s3d_set_error("decode stages: memcpy failed");
             return (int)hipErrorUnknown;
         }
-        // the three encoder layers + fc_out on groups [gs, gs + gn) of this pass, enqueued on stream s
-        const bool fold_ln = prec != S3D_PREC_F32;   // LayerNorm1 of the last layer in the final FFN kernel's prologue
-        auto run_layers = [&](hipStream_t s, long gs, long gn, hipEvent_t after_first_attn) -> int {
-            float* Xs = X + (size_t)gs * T * S3D_GROUP * 128;
-            float* X0s = X0 + (size_t)gs * S3D_GROUP * 128;
-            float* lasts = (float*)workspace + W.last + (size_t)gs * S3D_GROUP * S3D_LAST_ROW_FLOATS;
-            for (int l = 0; l < S3D_N_LAYERS; ++l) {
-                const LayerPtrs lp = layer_ptrs(b, H, l);
-                const bool last = l == S3D_N_LAYERS - 1;
-                {
-                    ProfScope prof_(S3D_PROF_ATTN, s);
-                    if (last)          // only token 0 of the last layer is consumed (models.py:83): absorbed form, every mode
-                        TRY(attn_last_layer(b, H, lp, Xs, X0s, gn, T, lasts, prec, s, fold_ln));
-                    else if (prec != S3D_PREC_F32)
-                        TRY(launch_attn_layer_q(Xs, gn, T, lp, s, prec == S3D_PREC_F16, bf16));
-                    else
-                        TRY(launch_attn_layer(Xs, nullptr, gn, T, lp, s));
-                }
-                if (l == 0 && after_first_attn && hipEventRecord(after_first_attn, s) != hipSuccess) {
-                    s3d_set_error("decode: hipEventRecord failed");
-                    return (int)hipErrorUnknown;
-                }
-                if (!last) {
-                    for (long f0 = 0; f0 < gn; f0 += S3D_FFN_LAUNCH_GROUPS) {   // (rows are independent: any split is the same result)
-                        const long fc = gn - f0 < S3D_FFN_LAUNCH_GROUPS ? gn - f0 : S3D_FFN_LAUNCH_GROUPS;
-                        ProfScope prof_(S3D_PROF_FFN, s);
-                        TRY(launch_ffn_layer(Xs + (size_t)f0 * T * S3D_GROUP * 128, fc * T * S3D_GROUP, lp, nullptr, nullptr, nullptr,
-                                             1.f, gpb, n_qry, g0 + gs + f0, ffn_prec, nullptr, s));
-                    }
-                    if (stages) TRY(launch_tok0_copy(Xs, stages + rows_all + (size_t)l * rows0_all, gn, T, 0, 128, s));
-                } else {
-                    ProfScope prof_(S3D_PROF_FFN_FINAL, s);
-                    if (stages) {   // the final kernel keeps the layer's output rows in registers (LayerNorm -> fc_out): the capture
-                                    // runs the full-row form of the same kernel on a copy of the token-0 rows
-                        float* d = stages + rows_all + (size_t)l * rows0_all;
-                        if (fold_ln) {   // X0 holds the pre-LayerNorm sums (the final kernel normalises them itself): the capture's copy is normalised here
-                            TRY(launch_ln_fwd(X0s, lp.ln1g, lp.ln1b, d, gn * S3D_GROUP, s));
-                        } else if (hipMemcpyAsync(d, X0s, rows0_all * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
-                            s3d_set_error("decode stages: memcpy failed");
-                            return (int)hipErrorUnknown;
-                        }
-                        TRY(launch_ffn_layer(d, gn * S3D_GROUP, lp, nullptr, nullptr, nullptr, 1.f, gpb, n_qry, g0 + gs, ffn_prec,
-                                             nullptr, s));
-                    }
-                    TRY(launch_ffn_layer(X0s, gn * S3D_GROUP, lp, b + H.fco_w, b + H.fco_b, out, sign, gpb, n_qry, g0 + gs,
-                                         ffn_prec, perm, s, fold_ln));
-                }
-            }
-            return 0;
-        };
+        D.g0 = g0;
         DecodeLanes* lanes = (!stages && prec != S3D_PREC_F32 && gc >= S3D_LANES_MIN_GROUPS && decode_lanes() == 2)
                                  ? decode_lanes_for_device() : nullptr;
         std::unique_lock<std::mutex> lanes_lock;
@@ -1048,18 +1094,18 @@ static int decode_impl(const void* head_packed, const S3dLatent* lat, const floa
             }
         }
         if (!lanes) {
-            TRY(run_layers(st, 0, gc, nullptr));
+            TRY(decode_layers(D, st, 0, gc));
         } else {
             // lane 0 = the first half on the caller's stream; lane 1 = the second half on the side stream, released when lane
             // 0's first attention launch is done (and with it the token builder): from then on one lane's attention phases
             // meet the other lane's FFN phases.  The device's mutex is held from the fork to the join (see DecodeLanes).
             const long h0 = (gc / 2 + 7) / 8 * 8;
-            TRY(run_layers(st, 0, h0, lanes->stagger));
+            TRY(decode_layers(D, st, 0, h0, lanes->stagger));
             if (hipStreamWaitEvent(lanes->aux, lanes->stagger, 0) != hipSuccess) {
                 s3d_set_error("decode: hipStreamWaitEvent failed");
                 return (int)hipErrorUnknown;
             }
-            const int rc = run_layers(lanes->aux, h0, gc - h0, nullptr);
+            const int rc = decode_layers(D, lanes->aux, h0, gc - h0);
             // join even on failure: the caller's stream must not run ahead of work already enqueued on the side stream
             if (hipEventRecord(lanes->join, lanes->aux) != hipSuccess || hipStreamWaitEvent(st, lanes->join, 0) != hipSuccess) {
                 s3d_set_error("decode: lane join failed");

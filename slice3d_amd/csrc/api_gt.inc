@@ -13,62 +13,24 @@ static const int kGtC[5] = {64, 128, 256, 512, 512};            // conv1_2 ... c
 static const int kGtCol[5] = {0, 64, 192, 448, 960};            // column offsets inside fc_local[0].weight (128,1472)
 
 struct GtEncLayout {
-    PackedConv enc[13];
-    size_t pool_scale[5], pool_shift[5];   // BN that follows each tap (conv_last's BN for the 5th is unused)
+    EncLayout E;
     size_t total;
 };
 static GtEncLayout gt_enc_layout() {
-    GtEncLayout L;
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        size_t o = off;
-        off += (n + 3) / 4 * 4;
-        return o;
-    };
-    for (int i = 0; i < 13; ++i) {
-        PackedConv& pc = L.enc[i];
-        pc.cout_pad = kEncCout[i];
-        pc.KU = 9 * pad16(kEncCin[i]) / 16;
-        pc.w = take((size_t)pc.cout_pad * pc.KU * 16);
-        pc.w16 = take((size_t)pc.cout_pad * pc.KU * 16);
-        pc.scale = take(pc.cout_pad);
-        pc.shift = take(pc.cout_pad);
-    }
-    for (int i = 0; i < 4; ++i) {
-        L.pool_scale[i] = take(kGtC[i]);
-        L.pool_shift[i] = take(kGtC[i]);
-    }
-    L.total = off;
-    return L;
+    ImageAlloc a;
+    const EncLayout E = enc_layout(a);
+    return GtEncLayout{E, a.off};
 }
 extern "C" size_t s3d_gt_encoder_packed_bytes(void) { return gt_enc_layout().total * sizeof(float); }
 
 extern "C" int s3d_gt_encoder_pack(const S3dVgg16BnParams* P, void* packed, size_t packed_bytes, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
     S3D_CHECK_ARG(P && packed, "gt_encoder_pack: null argument");
     const GtEncLayout L = gt_enc_layout();
     if (packed_bytes < L.total * sizeof(float)) {
         s3d_set_error("gt_encoder_pack: packed buffer %zu < %zu bytes", packed_bytes, L.total * sizeof(float));
         return S3D_E_WORKSPACE;
     }
-    float* base = (float*)packed;
-    for (int i = 0; i < 13; ++i) {
-        const PackedConv& pc = L.enc[i];
-        TRY(pack_conv3(P->conv[i].w, base + pc.w, kEncCout[i], pc.cout_pad, kEncCin[i], 0, kEncCin[i], pc.KU, 0, 9, st));
-        if (kEncCin[i] % 32 == 0)
-            TRY(pack_conv3(P->conv[i].w, base + pc.w16, kEncCout[i], pc.cout_pad, kEncCin[i], 0, kEncCin[i], pc.KU, 0, 9,
-                           st, 1));
-        if (kEncTap[i])   // tap: the raw conv output is the feature map (vgg16bn_feats.py:33-38 slice boundaries)
-            TRY(launch_fold_bn(P->conv[i].b, nullptr, base + pc.scale, base + pc.shift, kEncCout[i], pc.cout_pad, 1, 0, st));
-        else
-            TRY(launch_fold_bn(P->conv[i].b, P->conv[i].bn, base + pc.scale, base + pc.shift, kEncCout[i], pc.cout_pad, 1,
-                               1, st));
-    }
-    const int tapi[4] = {1, 3, 6, 9};
-    for (int i = 0; i < 4; ++i)
-        TRY(launch_fold_bn(nullptr, P->conv[tapi[i]].bn, base + L.pool_scale[i], base + L.pool_shift[i],
-                           kEncCout[tapi[i]], kEncCout[tapi[i]], 1, 0, st));
-    return 0;
+    return pack_encoder(P->conv, (float*)packed, L.E, (hipStream_t)stream);
 }
 
 struct GtEncWs {
@@ -99,7 +61,6 @@ extern "C" int s3d_gt_encode_fwd(const void* packed, const float* img_slices, co
                                  int S, int prec, void* workspace, size_t workspace_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     S3D_CHECK_ARG(prec == S3D_PREC_F32 || prec == S3D_PREC_F16X3 || prec == S3D_PREC_F16, "gt_encode: precision mode %d", prec);
-    struct PrecScope { PrecScope(int p) { g_desc_prec = p; } ~PrecScope() { g_desc_prec = S3D_PREC_F32; } } ps_(prec);
     S3D_CHECK_ARG(packed && img_slices && out && workspace, "gt_encode: null argument");
     S3D_CHECK_ARG(n_img >= 1 && S >= 16 && S % 16 == 0, "gt_encode: n_img=%d S=%d (S must be a multiple of 16)", n_img, S);
     S3D_CHECK_ARG(out->n_img == n_img && out->size == S, "gt_encode: pyramid handle mismatch");
@@ -109,36 +70,12 @@ extern "C" int s3d_gt_encode_fwd(const void* packed, const float* img_slices, co
         s3d_set_error("gt_encode: workspace %zu < %zu bytes", workspace_bytes, W.total * sizeof(float));
         return S3D_E_WORKSPACE;
     }
-    const float* base = (const float*)packed;
     float* ws = (float*)workspace;
     ProfScope prof_(S3D_PROF_UNET, st);
     TRY(launch_nchw_to_nhwc(img_slices, ws + W.in16, n_img, 3, S, S, 16, st));
-    const float* cur = ws + W.in16;
-    int curC = 16, res = S, tap_i = 0;
-    float* pp[2] = {ws + W.a, ws + W.b};
-    int flip = 0;
-    for (int i = 0; i < 13; ++i) {
-        ConvLaunch c = conv_desc(base, L.enc[i], n_img, res, res, 3, kEncTap[i] ? S3D_ACT_NONE : S3D_ACT_RELU);
-        c.nsrc = 1;
-        c.src[0] = plain_src(cur, curC);
-        c.splitk_ws = ws + W.splitk; c.splitk_floats = S3D_SPLITK_FLOATS;
-        float* dst = kEncTap[i] ? out->level[tap_i] : pp[flip];
-        c.out = dst;
-        TRY(launch_conv(c, st));
-        cur = dst;
-        curC = kEncCout[i];
-        if (!kEncTap[i]) flip ^= 1;
-        if (kEncTap[i]) {
-            if (tap_i < 4) {
-                TRY(launch_bn_relu_pool(out->level[tap_i], base + L.pool_scale[tap_i], base + L.pool_shift[tap_i],
-                                        ws + W.p[tap_i], n_img, res, res, curC, st));
-                cur = ws + W.p[tap_i];
-                res /= 2;
-            }
-            ++tap_i;
-        }
-    }
-    return 0;
+    float* const pp[2] = {ws + W.a, ws + W.b};
+    float* const pool[4] = {ws + W.p[0], ws + W.p[1], ws + W.p[2], ws + W.p[3]};
+    return encoder_fwd((const float*)packed, L.E, prec, n_img, S, 0, ws + W.in16, out->level, pp, pool, ws + W.splitk, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -221,39 +158,16 @@ extern "C" int s3d_gt_latent_build(const void* head_packed, const S3dGtPyramid* 
     ProfScope prof_(S3D_PROF_LATENT, st);
     for (int l = 0; l < 4; ++l) {
         const int lev = 4 - l, r = pyr->size >> lev, C = kGtC[lev];
-        ConvLaunch c = {};
-        c.N = pyr->n_img; c.H = r; c.W = r; c.ks = 1;
-        c.CoutPad = 128; c.wpk = b + G.wproj[l]; c.KU = C / 16;
-        c.wpk16 = prec != S3D_PREC_F32 ? (const void*)(b + G.wproj16[l]) : nullptr;
-        c.single_pass = prec == S3D_PREC_F16;
-        c.act = S3D_ACT_NONE; c.out_mode = S3D_OUT_NHWC; c.cout_store = 128; c.out_cstride = 128;
-        c.nsrc = 1;
-        c.src[0] = plain_src(pyr->level[lev], C);
-        c.out = out->proj[l];
-        TRY(launch_conv(c, st));
+        TRY(launch_conv(proj_desc(b + G.wproj[l], prec != S3D_PREC_F32 ? b + G.wproj16[l] : nullptr, prec == S3D_PREC_F16,
+                                  128, C, pyr->level[lev], pyr->n_img, r, r, out->proj[l]),
+                        st));
     }
     return 0;
 }
 
-struct GtDecodeWs {
-    size_t X, X2, X0, perm, sortws, last, total;
-};
-static GtDecodeWs gt_decode_ws(int batch, long n_qry, int ns) {
-    const long gpb = (n_qry + S3D_GROUP - 1) / S3D_GROUP;
-    long g = gpb * batch;
-    if (g > S3D_CHUNK_GROUPS) g = S3D_CHUNK_GROUPS;
-    GtDecodeWs W;
-    W.X = 0;
-    W.X2 = (size_t)g * (ns + 1) * S3D_GROUP * 128;
-    W.X0 = 2 * W.X2;
-    W.perm = W.X0 + (size_t)g * S3D_GROUP * 128;
-    W.sortws = W.perm + (size_t)batch * n_qry;
-    W.last = (W.sortws + query_sort_ws_ints(batch, n_qry) + 63) / 64 * 64;
-    W.total = W.last + (size_t)g * S3D_GROUP * S3D_LAST_ROW_FLOATS;
-    return W;
-}
+// the Reg decoder's workspace (decode_ws) at the fixed pass size, plus the token tensor X1 in front
 extern "C" size_t s3d_gt_decode_workspace_bytes(int batch, long n_qry, int n_slices) {
-    return gt_decode_ws(batch, n_qry, n_slices).total * sizeof(float);
+    return decode_ws(batch, n_qry, n_slices, S3D_CHUNK_GROUPS, true).total * sizeof(float);
 }
 
 static int gt_decode_impl(const void* head_packed, const S3dGtLatent* lat, const float* qry, const float* rot,
@@ -264,16 +178,15 @@ static int gt_decode_impl(const void* head_packed, const S3dGtLatent* lat, const
     S3D_CHECK_ARG(ns >= 1 && ns <= 12, "gt_decode: n_slices %d", ns);
     S3D_CHECK_ARG(lat->n_img == batch * ns, "gt_decode: latent has %d images, expected %d", lat->n_img, batch * ns);
     S3D_CHECK_ARG(prec == S3D_PREC_F32 || prec == S3D_PREC_F16X3 || prec == S3D_PREC_F16, "gt_decode: precision mode %d not built", prec);
-    const GtDecodeWs W = gt_decode_ws(batch, n_qry, ns);
+    const DecodeWs W = decode_ws(batch, n_qry, ns, S3D_CHUNK_GROUPS, true);   // fixed pass size: no smaller-pass fallback
     if (workspace_bytes < W.total * sizeof(float)) {
         s3d_set_error("gt_decode: workspace %zu < %zu bytes", workspace_bytes, W.total * sizeof(float));
         return S3D_E_WORKSPACE;
     }
     const GtHeadLayout G = gt_head_layout();
     const float* b = (const float*)head_packed;
-    float* X1 = (float*)workspace + W.X;
-    float* X = (float*)workspace + W.X2;
-    float* X0 = (float*)workspace + W.X0;
+    float* X1 = (float*)workspace + W.X1;
+    float* X = (float*)workspace + W.X;
     const int T = ns + 1;
     const long gpb = (n_qry + S3D_GROUP - 1) / S3D_GROUP;
     const long Gn = gpb * batch;
@@ -284,6 +197,8 @@ static int gt_decode_impl(const void* head_packed, const S3dGtLatent* lat, const
                               (int*)((float*)workspace + W.sortws), st));
         perm = pm;
     }
+    DecodeStack D{b, G.H, X, (float*)workspace + W.X0, (float*)workspace + W.last, T, prec, false, false, gpb, n_qry, 0,
+                  out, sign, perm, nullptr};
     for (long g0 = 0; g0 < Gn; g0 += S3D_CHUNK_GROUPS) {
         const long gc = Gn - g0 < S3D_CHUNK_GROUPS ? Gn - g0 : S3D_CHUNK_GROUPS;
         {
@@ -299,17 +214,8 @@ static int gt_decode_impl(const void* head_packed, const S3dGtLatent* lat, const
             sa.nx = nx; sa.box = box; sa.X = X1; sa.perm = perm;
             TRY(launch_sample_tokens_gt(sa, st));
             // fc_local[2] + ReLU on every row (token-0 rows are overwritten right after)
-            ConvLaunch c = {};
-            c.N = 1; c.H = 1; c.W = (int)(gc * T * S3D_GROUP); c.ks = 1;
-            c.CoutPad = 128; c.wpk = b + G.wl1; c.KU = 8;
-            c.wpk16 = prec != S3D_PREC_F32 ? (const void*)(b + G.wl1_16) : nullptr;
-        c.single_pass = prec == S3D_PREC_F16;
-            c.shift = b + G.bl1; c.act = S3D_ACT_RELU;
-            c.out_mode = S3D_OUT_NHWC; c.cout_store = 128; c.out_cstride = 128;
-            c.nsrc = 1;
-            c.src[0] = plain_src(X1, 128);
-            c.out = X;
-            TRY(launch_conv(c, st));
+            TRY(rows_linear(b, G.wl1, G.wl1_16, 128, 128, b + G.bl1, X1, gc * T * S3D_GROUP, X, nullptr, prec, st,
+                            S3D_ACT_RELU));
             GtPointArgs pa = {};
             pa.w0 = b + G.pw0; pa.b0 = b + G.pb0; pa.w1 = b + G.pw1; pa.b1 = b + G.pb1; pa.w2 = b + G.pw2; pa.b2 = b + G.pb2;
             pa.qry = qry; pa.rot = rot; pa.flip_yz = flip_yz; pa.n_slices = ns;
@@ -317,26 +223,8 @@ static int gt_decode_impl(const void* head_packed, const S3dGtLatent* lat, const
             pa.nx = nx; pa.box = box; pa.X = X; pa.perm = perm;
             TRY(launch_gt_point_tokens(pa, st));
         }
-        for (int l = 0; l < S3D_N_LAYERS; ++l) {
-            const LayerPtrs lp = layer_ptrs(b, G.H, l);
-            const bool last = l == S3D_N_LAYERS - 1;
-            {
-                ProfScope prof_(S3D_PROF_ATTN, st);
-                if (last)
-                    TRY(attn_last_layer(b, G.H, lp, X, X0, gc, T, (float*)workspace + W.last, prec, st));
-                else if (prec != S3D_PREC_F32)
-                    TRY(launch_attn_layer_q(X, gc, T, lp, st, prec == S3D_PREC_F16));
-                else
-                    TRY(launch_attn_layer(X, nullptr, gc, T, lp, st));
-            }
-            ProfScope prof_(last ? S3D_PROF_FFN_FINAL : S3D_PROF_FFN, st);
-            if (!last)
-                TRY(launch_ffn_layer(X, gc * T * S3D_GROUP, lp, nullptr, nullptr, nullptr, 1.f, gpb, n_qry, g0, prec,
-                                     nullptr, st));
-            else
-                TRY(launch_ffn_layer(X0, gc * S3D_GROUP, lp, b + G.H.fco_w, b + G.H.fco_b, out, sign, gpb, n_qry, g0,
-                                     prec, perm, st));
-        }
+        D.g0 = g0;
+        TRY(decode_layers(D, st, 0, gc));
     }
     return 0;
 }

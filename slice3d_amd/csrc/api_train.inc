@@ -594,18 +594,11 @@ struct DecoderTrain {
     int lin(const FragW& wf, int n, int k, const float* bias, const float* x, long nrows, float* out,
             const float* residual, int accumulate, const DropCfg* dc = nullptr, int act = S3D_ACT_NONE,
             unsigned long long drop_base = 0, const float* gate = nullptr, float gate_scale = 1.f) const {
-        ConvLaunch c = {};
+        const float* p16 = prec == S3D_PREC_F16X3 ? wf.p16 : nullptr;
+        ConvLaunch c = proj_desc(wf.p, p16, single && p16, n, k, x, 1, 1, (int)nrows, out, bias, act);
         if (dc) c.drop = *dc;
         c.drop_base = drop_base; c.gate = gate; c.gate_scale = gate_scale;
-        c.N = 1; c.H = 1; c.W = (int)nrows; c.ks = 1;
-        c.CoutPad = n; c.wpk = wf.p; c.KU = k / 16;
-        c.wpk16 = prec == S3D_PREC_F16X3 ? (const void*)wf.p16 : nullptr;
-        c.single_pass = single && c.wpk16;
-        c.scale = nullptr; c.shift = bias; c.act = act;
-        c.out_mode = S3D_OUT_NHWC; c.cout_store = n; c.out_cstride = n;
-        c.nsrc = 1;
-        c.src[0] = plain_src(x, k);
-        c.out = out; c.residual = residual; c.out_accumulate = accumulate;
+        c.residual = residual; c.out_accumulate = accumulate;
         return launch_conv(c, st);
     }
     // split-precision training runs the attention block of the full layers as fused query-major kernels
@@ -940,16 +933,10 @@ static int train_step_impl(const S3dUNetParams* U, const S3dHeadParams* Hd, cons
     // 3. decoder forward (models.py:53-84), activations kept
     // =========================================================================================
     range.next("s3d:train:sample_and_decoder_fwd");
-    for (int l = 0; l < 3; ++l) {
+    for (int l = 0; l < 3; ++l) {   // fp32 in every mode
         const int r = r5 << l;
-        ConvLaunch c = {};
-        c.N = Nd; c.H = r; c.W = r; c.ks = 1;
-        c.CoutPad = 128; c.wpk = T.head_packed + HL.wproj[l]; c.KU = lc[l] / 16;
-        c.act = S3D_ACT_NONE; c.out_mode = S3D_OUT_NHWC; c.cout_store = 128; c.out_cstride = 128;
-        c.nsrc = 1;
-        c.src[0] = plain_src(T.F[l], lc[l]);
-        c.out = T.lat_proj[l];
-        TRY(launch_conv(c, st));
+        TRY(launch_conv(proj_desc(T.head_packed + HL.wproj[l], nullptr, false, 128, lc[l], T.F[l], Nd, r, r, T.lat_proj[l]),
+                        st));
     }
     {
         SampleArgs sa = {};

@@ -108,15 +108,9 @@ extern "C" int s3d_gt_train_fwd_bwd(const S3dVgg16BnParams* E, const S3dGtHeadPa
     TRY(enc_forward(R, E->conv, batch->img_slices, Nd, S, 1));
     for (int l = 0; l < 4; ++l) {   // fc_local[0] folded into conv5_3 ... conv2_2
         const int lev = 4 - l, r = r5 << l, C = kGtC[lev];
-        ConvLaunch c = {};
-        c.N = Nd; c.H = r; c.W = r; c.ks = 1;
-        c.CoutPad = 128; c.wpk = hb + GL.wproj[l]; c.KU = C / 16;
-        c.wpk16 = prec == S3D_PREC_F16X3 ? (const void*)(hb + GL.wproj16[l]) : nullptr;
-        c.act = S3D_ACT_NONE; c.out_mode = S3D_OUT_NHWC; c.cout_store = 128; c.out_cstride = 128;
-        c.nsrc = 1;
-        c.src[0] = plain_src(T.z[kTapConv[lev]], C);
-        c.out = X.gproj[l];
-        TRY(launch_conv(c, st));
+        TRY(launch_conv(proj_desc(hb + GL.wproj[l], prec == S3D_PREC_F16X3 ? hb + GL.wproj16[l] : nullptr, false, 128, C,
+                                  T.z[kTapConv[lev]], Nd, r, r, X.gproj[l]),
+                        st));
     }
 
     // ---- 3. tokens (model_gt.py:78-99) ----
