@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define S3D_VERSION 115          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd */
+#define S3D_VERSION 116          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd */
 #define S3D_E_ARG (-1)           /* bad argument / unsupported shape */
 #define S3D_E_WORKSPACE (-2)     /* workspace or packed-weight buffer too small */
 
@@ -362,6 +362,24 @@ int s3d_add_fwd(const float* a, const float* b, float* out, long n, void* stream
 int s3d_nchw_to_nhwc_pad(const float* in, float* out, int n, int c, int h, int w, int cpad, void* stream);
 /* out (N,H,W,C) = a (N,H,W,C) + b (N,C,H,W): the same injection with the feature map taken as the reference hands it over (version 115) */
 int s3d_add_nchw_fwd(const float* a, const float* b, float* out, int n, int c, int h, int w, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * First-stage AutoencoderKL (gen_slices/ldm/modules/diffusionmodules/model.py) and condition encoder ImageEncoderVGG16BN
+ * (ldm/modules/encoders/modules.py:204-267) — version 116.  The other layers run on the U-Net primitives above.
+ * ------------------------------------------------------------------------------------------- */
+/* Strided Conv2d on the packed image of s3d_conv_pack (cin1 = 0): x (N,Hin,Win,pad16(cin)) -> out (N,Hout,Wout,cout);
+ * input pixel = stride * out + tap - pad, zeros outside the input.  pad = ks / 2; pad_origin = 1 (ks 3, stride > 1):
+ * pad 0 at the top / left — Downsample's F.pad(x, (0,1,0,1)) + Conv2d(3, stride 2) (model.py:60-79).  ks 1 with stride s:
+ * a 1x1 convolution followed by a nearest s-fold downsize, computed on the picked pixels only (modules.py:262-266).
+ * prec: S3D_PREC_F32 or S3D_PREC_F16X3. */
+int s3d_conv_strided_fwd(const void* packed, const float* x, float* out, int N, int Hin, int Win, int Hout, int Wout, int cout,
+                         int cin, int ks, int stride, int pad_origin, int prec, void* stream);
+/* AttnBlock (model.py:150-202): one head of width C (64, 128, 256 or 512) over T >= 1 tokens, softmax(q k^T C^-0.5) v;
+ * qkv (N, T, 3C) rows q | k | v -> out (N, T, C).  prec: S3D_PREC_F32 or S3D_PREC_F16X3 (both exact fp32 arithmetic). */
+int s3d_wide_attention_fwd(const float* qkv, float* out, int N, int T, int C, int prec, void* stream);
+/* ImageEncoderVGG16BN's input normalisation (modules.py:251-253): y = ((x + 1) / 2 - mean[c]) / std[c], x and y (n,c,h,w) */
+int s3d_image_normalize_fwd(const float* x, const float* mean, const float* std, float* y, int n, int c, int h, int w,
+                            void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training step — replaces train_step (reg_slices/train.py:41-53): train-mode forward (batch-statistic

@@ -36,6 +36,8 @@ struct ConvLaunch {
     int ks;              // 1, 3 (pad 1) or 2 (pad 0; with stride 2 = the data-gradient of ConvTranspose2d 2x2 s2)
     int stride;          // 0/1 = 1; 2: input pixel = 2*out + tap offset, input grid is (Hin, Win)
     int Hin, Win;        // input spatial size (0 = same as H, W)
+    int pad_origin;      // 0: top / left pad ks / 2 (1 for ks 3, else 0); 1 (ks 3 with stride > 1 only): no top / left pad —
+                         // input pixel = stride * out + tap, zeros beyond the bottom / right edge (Downsample's F.pad (0,1,0,1))
     int CoutPad;         // GEMM N, multiple of 16 (padded rows of the packed weight are zero)
     const float* wpk;    // packed A fragments [CoutPad/16][KU][64][4]
     int KU;              // total K chunks = sum over sources of ks*ks*C/16

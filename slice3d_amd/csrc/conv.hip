@@ -170,7 +170,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(const ConvLaunc
     const int HW = a.H * a.W;
     const int stride = a.stride > 1 ? a.stride : 1;
     const int Hin = a.Hin ? a.Hin : a.H, Win = a.Win ? a.Win : a.W;
-    constexpr int PAD = KS == 3 ? 1 : 0;
+    const int PAD = a.pad_origin ? 0 : (KS == 3 ? 1 : 0);
 
     int pn[MT], py[MT], px[MT];
     bool pv[MT];
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_f16x3_kernel(const Con
     const int HW = a.H * a.W;
     const int stride = a.stride > 1 ? a.stride : 1;
     const int Hin = a.Hin ? a.Hin : a.H, Win = a.Win ? a.Win : a.W;
-    constexpr int PAD = KS == 3 ? 1 : 0;
+    const int PAD = a.pad_origin ? 0 : (KS == 3 ? 1 : 0);
     const int KU32 = a.KU >> 1;
     const _Float16* wimg = reinterpret_cast<const _Float16*>(a.wpk16);
 
@@ -1370,6 +1370,8 @@ int launch_conv(const ConvLaunch& a_in, hipStream_t stream) {
     ConvLaunch a = a_in;
     a.xcd_remap = 1;   // block -> (pixel tile, cout tile) mapping keeps the cout tiles of a pixel tile on one XCD
     S3D_CHECK_ARG(a.ks >= 1 && a.ks <= 3, "conv: ks must be 1, 2 or 3");
+    S3D_CHECK_ARG(!a.pad_origin || (a.ks == 3 && a.stride > 1 && a.out_mode == S3D_OUT_NHWC),
+                  "conv: pad_origin is served for strided 3x3 convolutions only");
     S3D_CHECK_ARG(a.CoutPad % 16 == 0 && a.CoutPad > 0, "conv: CoutPad %d", a.CoutPad);
     for (int s = 0; s < a.nsrc; ++s)
         S3D_CHECK_ARG(a.src[s].C % 16 == 0 && a.src[s].bdiv >= 1, "conv: bad source %d", s);

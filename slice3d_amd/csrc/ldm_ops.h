@@ -28,3 +28,8 @@ int launch_small_linear(const float* x, const float* w, const float* b, float* o
                         hipStream_t stream);
 int launch_timestep_embedding(const float* t, float* out, int N, int dim, float max_period, hipStream_t stream);
 int launch_add(const float* a, const float* b, float* out, long n, hipStream_t stream);
+// ldm_ae.hip: the first-stage autoencoder's single-head attention (C = 64, 128, 256 or 512; qkv (N, T, 3C) rows q | k | v) and
+// the condition encoder's input normalisation ((x + 1) / 2 - mean) / std over NCHW images
+int launch_wide_attention(const float* qkv, float* out, int N, int T, int C, hipStream_t stream);
+int launch_image_normalize(const float* x, const float* mean, const float* stdv, float* y, int n, int c, long hw,
+                           hipStream_t stream);
