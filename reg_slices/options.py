@@ -67,6 +67,11 @@ _BUILD_FLAGS = [
     ("prec", dict(type=str, default="f32", choices=["f32", "f16x3", "f16"],
                   help="[build] train.py: arithmetic of the step's GEMMs — f32 (exact fp32 MFMAs), f16x3 (split precision, fp32-class, "
                        "~1.5x faster) or f16 (single-pass throughput mode of the decoder, a further 1.3x, not fp32-class)")),
+    ("gen_ckpt", dict(type=str, default="", help="[build] reconstruct.py --name_model gtslice --from_which_slices gen: "
+                                                 "generate the slices in memory with this LatentDiffusion checkpoint "
+                                                 "instead of reading 04_img_slices_gen")),
+    ("ddim_steps", dict(type=int, default=200, help="[build] DDIM steps of the in-memory gen route")),
+    ("gen_seed", dict(type=int, default=0, help="[build] seed of the in-memory gen route's noise")),
 ]
 
 

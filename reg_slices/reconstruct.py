@@ -4,10 +4,16 @@ load a checkpoint into Slices3DRegModel(mode='test'), run Generator3D (MISE or d
 
     python reg_slices/reconstruct.py --name_exp demo --name_ckpt x.ckpt --name_dataset synthetic \
         --mode test --img_size 128 --mc_res0 64 --mc_up_steps 2
+
+With --name_model gtslice --from_which_slices gen --gen_ckpt <LatentDiffusion .ckpt> the slices are generated in memory
+(slice3d_amd/gen_route.py): per batch of --n_bs test objects, input view 004 -> SliceDiffusion.generate -> the 8-bit mosaic
+quantisation of test_step -> the GT model, the same bits the file route (gen_slices/sample_slices.py + re_org_slices.py)
+gives it, without writing or reading slice images.
 """
 import os
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -49,6 +55,10 @@ def main():
         dataset = Slice3DDataset(split="test", args=args)
     else:
         dataset = SyntheticSlice3DDataset(args.synthetic_len, args.img_size, 16, args.n_slices, split="test")
+    if args.gen_ckpt:
+        if args.name_model != "gtslice" or args.from_which_slices != "gen" or args.name_dataset == "synthetic":
+            raise SystemExit("--gen_ckpt needs --name_model gtslice --from_which_slices gen and an on-disk dataset")
+        return reconstruct_generated(args, generator, path_res)
     with torch.no_grad():
         for idx in range(len(dataset)):
             shape = dataset.files[idx][1] if hasattr(dataset, "files") else "synthetic_%04d" % idx
@@ -59,6 +69,39 @@ def main():
             mesh, stats = generator.generate_mesh(data)
             mesh.export(path_mesh)
             print(path_mesh, "%d verts %d faces" % (len(mesh.vertices), len(mesh.faces)), stats)
+
+
+def reconstruct_generated(args, generator, path_res):
+    """The in-memory gen route: one generate() per batch of test objects, then a mesh per object."""
+    from slice3d_amd import gen_route
+    from slice3d_amd.datasets import Slice3DDataset
+    if os.path.isfile(args.gen_ckpt):
+        diffusion = gen_route.load_ldm_checkpoint(args.gen_ckpt)
+    elif args.synthetic_weights:
+        print("LDM checkpoint %s not found: --synthetic_weights -> name-seeded random weights" % args.gen_ckpt)
+        diffusion = gen_route.synthetic_slice_diffusion(0)
+    else:
+        raise FileNotFoundError("LDM checkpoint %s not found" % args.gen_ckpt)
+    diffusion = diffusion.cuda().eval()
+    dataset = Slice3DDataset(split="test", args=args, with_slices=False)
+    views = gen_route.ObjaverseLdmDataset(dataset.dir_dataset, "test", size=args.img_size, with_slices=False)
+    todo = [idx for idx in range(len(dataset)) if args.overwrite_res or
+            not os.path.exists(os.path.join(path_res, dataset.files[idx][1] + ".obj"))]
+    rng = torch.Generator(device="cuda").manual_seed(args.gen_seed)
+    with torch.no_grad():
+        for lo in range(0, len(todo), args.n_bs):
+            chunk = todo[lo:lo + args.n_bs]
+            ipt = np.stack([views.input_view(dataset.files[idx][1]) for idx in chunk])
+            img = torch.from_numpy((ipt / 127.5 - 1.0).astype(np.float32)).permute(0, 3, 1, 2).contiguous()
+            slices = diffusion.generate(img, ddim_steps=args.ddim_steps, eta=1.0, generator=rng)
+            img_slices = gen_route.gen_slices_to_model_input(gen_route.slices_to_mosaic_u8(slices))
+            for j, idx in enumerate(chunk):
+                path_mesh = os.path.join(path_res, dataset.files[idx][1] + ".obj")
+                data = {k: v.unsqueeze(0).cuda() for k, v in dataset[idx].items()}
+                data["img_slices"] = img_slices[j:j + 1]
+                mesh, stats = generator.generate_mesh(data)
+                mesh.export(path_mesh)
+                print(path_mesh, "%d verts %d faces" % (len(mesh.vertices), len(mesh.faces)), stats)
 
 
 if __name__ == "__main__":

@@ -78,8 +78,10 @@ def _to_tensor_normalised(img):
 class Slice3DDataset(Dataset):
     SLICE_ORDER = (("X", "1234"), ("Z", "4321"), ("Y", "1234"))
 
-    def __init__(self, split, args):
+    def __init__(self, split, args, with_slices=True):
+        """with_slices=False: items carry everything but img_slices (the in-memory gen route supplies those itself)."""
         self.split = split
+        self.with_slices = with_slices
         self.n_qry = args.n_qry
         self.dir_dataset = os.path.join(args.dir_data, args.name_dataset)
         self.name_dataset = args.name_dataset
@@ -126,12 +128,11 @@ class Slice3DDataset(Dataset):
         tag = "%03d" % view
         img_ipt = self._rgba(Image.open(os.path.join(self.dir_img_ipt, shape_id, tag + ".png")))
         slices = []
-        for axis, parts in self.SLICE_ORDER:
+        for axis, parts in (self.SLICE_ORDER if self.with_slices else ()):
             for part in parts:
                 im = Image.open(os.path.join(self.dir_img_slice, shape_id, tag, "%s_%s.png" % (axis, part)))
                 slices.append(_to_tensor_normalised(im) if self.from_which_slices in ("gen", "gt_rec")
                               else self._rgba(im))
-        img_slices = torch.cat(slices, 0)
 
         with open(os.path.join(self.dir_img_ipt, shape_id, "meta.pkl"), "rb") as f:
             meta = pickle.load(f)
@@ -147,15 +148,17 @@ class Slice3DDataset(Dataset):
         else:
             np.random.seed(1234)
         perm = np.random.permutation(len(qry))[:self.n_qry]
-        return {
+        item = {
             "img_input": img_ipt,
             "qry_norot": torch.tensor(qry[perm]).float(),
             "obj_rot_mat": torch.tensor(obj_rot_mat).float(),
             "trans_mat_wo_rot_tp": torch.tensor(trans_tp).float(),
             "occ": torch.tensor(occ[perm]).float(),
             "sdf": torch.tensor(sdf[perm]).float(),
-            "img_slices": img_slices,
         }
+        if self.with_slices:
+            item["img_slices"] = torch.cat(slices, 0)
+        return item
 
 
 def write_toy_dataset(root, name="toy", shapes=("shape_a", "shape_b"), n_views=6, size=40, n_pts=500, seed=0):
