@@ -8,7 +8,14 @@ split into f16 hi+lo and multiplied with 3 f16 MFMAs per product (fp32-class, pa
 --prec f32: exact fp32 MFMA.
 N GPUs = N independent objects (one process per GPU, no data-path collective): weak scaling.
 
+A plain run sets up, warms up, times the steps and prints the line: its roofline figures come from the timed steps'
+own per-stage times (HBM traffic quoted from profiles/pmc_traffic.json).  --full adds every secondary leg, each
+timed on its own after the headline steps: the CPU baseline and its parity check, the stand-alone feature-sample
+roofline, the in-run rocprofv3 traffic passes, the other precisions, white-noise inputs, the dense grid, mesh
+extraction, the LDM denoise step and the training steps (their --*-steps options size them).
+
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -30,6 +37,9 @@ F16_MFMA_PEAK_TFLOPS = 2500.0       # MI355X_MICROARCH.md: dense f16/bf16 MFMA p
 FFN_FLOP_PER_ROW = 2 * 2 * 128 * 2048   # two 128x2048 GEMMs, 2 FLOP/MAC (FFN = 88 %)
 F_MIN_PER_QUERY = 35.96e6           # exact decoder FLOPs/query with last-layer pruning
 ATTN_FLOP_PER_TOKEN = 2 * (3 * 128 * 128 + 128 * 128) + 2 * 2 * 13 * 128   # in_proj + out_proj + (QK^T, PV) over 13 keys
+# the option of every secondary leg with its size in a --full run (0 = the leg is skipped; a plain run skips them all)
+FULL_LEGS = {"cpu_sample": 8192, "f16_steps": 5, "f32_steps": 3, "noise_steps": 30, "c4_steps": 2, "mesh_steps": 2,
+             "ldm_steps": 20, "pmc": 1, "train_steps": 10, "gt_train_steps": 5, "train_f16_steps": 8}
 
 
 def _r(x, nd=4):
@@ -245,7 +255,9 @@ def _self_launch(n):
     return subprocess.call(cmd, env=env)
 
 
-def main():
+def parse_args(argv=None):
+    """The command line, with every secondary leg's option resolved: its FULL_LEGS size (or the size given) under --full,
+    0 otherwise; args.full is False under --infer-only."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -254,39 +266,49 @@ def main():
     ap.add_argument("--n-qry", type=int, default=100000)
     ap.add_argument("--n-slices", type=int, default=12)
     ap.add_argument("--batch", type=int, default=4, help="objects per GPU per step (BASELINE C2: B = 1..4)")
-    ap.add_argument("--cpu-sample", type=int, default=8192, help="queries timed on the CPU baseline (0 = skip)")
-    ap.add_argument("--cpu-runs", type=int, default=5, help="timed runs per stage of the CPU baseline (median; BASELINE.md section 4)")
     ap.add_argument("--prec", default="f16x3", choices=["f32", "f16x3"], help="arithmetic mode of the decoder GEMMs")
-    ap.add_argument("--f16-steps", type=int, default=5, help="timed steps of the single-pass f16 throughput mode, reported "
-                                                              "separately with its error (0 = skip)")
-    ap.add_argument("--f32-steps", type=int, default=3, help="timed steps of the exact fp32-MFMA mode, reported beside the headline "
-                                                              "(0 = skip)")
-    ap.add_argument("--noise-steps", type=int, default=30, help="timed steps on white-noise images with the clock sampled "
-                                                                "(SURVEY 8(d)'s inputs; 0 = skip)")
-    ap.add_argument("--c4-steps", type=int, default=2, help="timed dense 256^3 grid evaluations (BASELINE configs[3]; 0 = skip)")
+    ap.add_argument("--full", action="store_true", help="after the headline steps, run every secondary leg (sized by the "
+                    "options below; a plain run times the headline steps alone)")
+    # the secondary legs: each option below needs --full and defaults to FULL_LEGS' value there
+    ap.add_argument("--cpu-sample", type=int, help="queries timed on the CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-runs", type=int, default=5, help="timed runs per stage of the CPU baseline (median; BASELINE.md section 4)")
+    ap.add_argument("--f16-steps", type=int, help="timed steps of the single-pass f16 throughput mode, reported separately with "
+                                                   "its error (0 = skip)")
+    ap.add_argument("--f32-steps", type=int, help="timed steps of the exact fp32-MFMA mode, reported beside the headline (0 = skip)")
+    ap.add_argument("--noise-steps", type=int, help="timed steps on white-noise images with the clock sampled (SURVEY 8(d)'s "
+                                                     "inputs; 0 = skip)")
+    ap.add_argument("--c4-steps", type=int, help="timed dense 256^3 grid evaluations (BASELINE configs[3]; 0 = skip)")
     ap.add_argument("--c4-res", type=int, default=256)
-    ap.add_argument("--mesh-steps", type=int, default=2, help="timed reconstruct.py-default mesh extractions (MISE 64 -> 256 + "
-                    "marching cubes on the device; 0 = skip)")
-    ap.add_argument("--ldm-steps", type=int, default=20, help="timed LDM denoising steps (BASELINE configs[4]; 0 = skip)")
-    ap.add_argument("--pmc", type=int, default=1, help="1: measure roofline.traffic in this run (two rocprofv3 --pmc child passes "
-                    "of the timed inference loop, FETCH_SIZE and WRITE_SIZE); 0: quote the committed profiles/pmc_traffic.json")
+    ap.add_argument("--mesh-steps", type=int, help="timed reconstruct.py-default mesh extractions (MISE 64 -> 256 + marching "
+                    "cubes on the device; 0 = skip)")
+    ap.add_argument("--ldm-steps", type=int, help="timed LDM denoising steps (BASELINE configs[4]; 0 = skip)")
+    ap.add_argument("--pmc", type=int, help="1: measure roofline.traffic in this run (two rocprofv3 --pmc child passes of the "
+                    "timed inference loop, FETCH_SIZE and WRITE_SIZE); 0: quote the committed profiles/pmc_traffic.json")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # the child pass: inference loop only
-    ap.add_argument("--train-steps", type=int, default=10, help="timed training steps for train_samples_per_s (0 = skip)")
-    ap.add_argument("--gt-train-steps", type=int, default=5, help="timed Slices3DGTModel training steps (0 = skip)")
-    ap.add_argument("--train-f16-steps", type=int, default=8,
+    ap.add_argument("--train-steps", type=int, help="timed training steps for train_samples_per_s (0 = skip)")
+    ap.add_argument("--gt-train-steps", type=int, help="timed Slices3DGTModel training steps (0 = skip)")
+    ap.add_argument("--train-f16-steps", type=int,
                     help="timed steps of the training step's single-pass f16 throughput mode (prec='f16'; reported beside "
                          "train_ms_per_step with its gradient deviation, never instead of it; 0 = skip)")
-    ap.add_argument("--infer-only", action="store_true", help="the headline loop alone (A/B scripts): every secondary leg off")
+    ap.add_argument("--infer-only", action="store_true", help="the headline loop alone, --full or not (A/B scripts)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last of them returned (rank 0's "
                     "sdf_pred, batch x n_qry) to DIR/sdf_pred.npy in float32, to compare two builds output for output; past "
                     "64 MB a fixed seeded sample of it")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-    if args.infer_only:
-        for k in ("cpu_sample", "f16_steps", "f32_steps", "noise_steps", "c4_steps", "mesh_steps", "ldm_steps", "train_steps",
-                  "gt_train_steps", "train_f16_steps", "pmc"):
-            setattr(args, k, 0)
+    args.full = args.full and not args.infer_only
+    if not args.full and not args.infer_only:
+        on = ["--" + k.replace("_", "-") for k in FULL_LEGS if getattr(args, k)]
+        if on:
+            ap.error("%s: secondary legs run with --full only" % ", ".join(on))
+    for k, v in FULL_LEGS.items():
+        setattr(args, k, (v if getattr(args, k) is None else getattr(args, k)) if args.full else 0)
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: spawn the N ranks ourselves (one process per GPU under torch.distributed.run on
@@ -319,7 +341,7 @@ def main():
 
     model = Slices3DRegModel(img_size=args.img_size, n_slices=args.n_slices, mode="test", prec=args.prec)
     load_seeded(model, 0)
-    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if rank == 0 else None
+    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if rank == 0 and args.cpu_sample > 0 else None
     model.cuda().eval()
     fd = make_feed_dict(args.batch, args.img_size, args.n_qry, args.n_slices, seed=1234 + rank, with_slices=False,
                         device="cuda")
@@ -365,7 +387,7 @@ def main():
 
     # ---- secondary rooflines (north_star): stand-alone feature-sample op (HBM bound) ----
     sample_roof = None
-    if rank == 0:
+    if args.full and rank == 0:
         fd1 = {k: v[:1].contiguous() for k, v in fd.items()}      # one object: the (12, Q, 992) tensor is 4.8 GB
         code = model.encode(fd1, build_latent=False)
         g = model.project_coord(fd1["qry_norot"] * torch.tensor([1.0, -1.0, -1.0], device="cuda"),   # mode='test' flip

@@ -90,9 +90,9 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     cpu_baseline fields the driver and the judge read, whole-job value consistent with ms_per_step, parity inside."""
     import json
     out = run([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1", "--n-qry", "4096",
-               "--img-size", "64", "--cpu-sample", "256", "--cpu-runs", "1", "--train-steps", "1", "--c4-steps", "1", "--c4-res", "32",
-               "--ldm-steps", "0", "--gt-train-steps", "0", "--f16-steps", "1", "--mesh-steps", "0", "--f32-steps", "1",
-               "--noise-steps", "2"], ROOT)
+               "--img-size", "64", "--full", "--cpu-sample", "256", "--cpu-runs", "1", "--train-steps", "1", "--c4-steps", "1",
+               "--c4-res", "32", "--ldm-steps", "0", "--gt-train-steps", "0", "--f16-steps", "1", "--mesh-steps", "0",
+               "--f32-steps", "1", "--noise-steps", "2"], ROOT)
     lines = [ln for ln in out.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
     assert len(lines[0]) < 4096, len(lines[0])         # the driver keeps ~2 KB of the tail: the line stays short
@@ -125,6 +125,27 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert r["ms_per_step_rank_min_max"][0] <= r["ms_per_step_rank_min_max"][1]
 
 
+def test_bench_plain_run_times_the_headline_steps_alone():
+    """bench.py without --full: the same contract line, its roofline from the timed steps' stage times, and no secondary leg
+    run (no CPU baseline, no parity check, every leg's result null)."""
+    import json
+    out = run([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1", "--n-qry", "4096",
+               "--img-size", "64"], ROOT)
+    lines = [ln for ln in out.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    r = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "roofline"):
+        assert k in r, k
+    assert r["unit"] == "query-points/s" and r["steps"] == 2 and r["warmup"] == 1 and r["dtype"] == "f16x3"
+    assert abs(r["value"] - 4096 / (r["ms_per_step"] * 1e-3)) < 1e-6 * r["value"]
+    assert r["roofline"]["achieved"] > 0 and r["roofline"]["launches"] > 0
+    assert "cpu_baseline" not in r and "parity_vs_oracle" not in r and r["secondary_rooflines"][0] is None
+    for k in ("exact_f32_mode", "white_noise", "throughput_mode_f16", "throughput_mode_bf16", "c4_dense_grid", "ldm_denoise_step",
+              "mesh_extraction", "gt_train_step", "train_throughput_mode_f16", "train_ms_per_step", "train_samples_per_s"):
+        assert r[k] is None, k
+
+
 def test_bench_dump_outputs_is_the_same_for_the_same_arguments(tmp_path):
     """bench.py --dump-outputs DIR: the last timed step's sdf_pred (batch x n_qry, float32) lands in DIR/sdf_pred.npy with the
     JSON line still the only line on stdout; the inputs are seeded, so runs with other step counts write the same array."""
@@ -150,7 +171,7 @@ def test_bench_self_launches_two_ranks_on_one_gpu():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "1",
-           "--n-qry", "4096", "--img-size", "64", "--cpu-sample", "0", "--train-steps", "1", "--c4-steps", "1",
+           "--n-qry", "4096", "--img-size", "64", "--full", "--cpu-sample", "0", "--train-steps", "1", "--c4-steps", "1",
            "--c4-res", "32", "--ldm-steps", "1", "--gt-train-steps", "0", "--f16-steps", "0", "--mesh-steps", "0",
            "--f32-steps", "0", "--noise-steps", "0"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=1500, env=env)

@@ -48,7 +48,7 @@ def test_bench_runs_one_rank_per_device_over_rccl(n):
     for k in ("S3D_BENCH_BACKEND", "WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--batch", "1",
-                        "--n-qry", "20000", "--img-size", "128", "--cpu-sample", "0", "--train-steps", "2", "--c4-steps", "1",
+                        "--n-qry", "20000", "--img-size", "128", "--full", "--cpu-sample", "0", "--train-steps", "2", "--c4-steps", "1",
                         "--c4-res", "64", "--ldm-steps", "2", "--gt-train-steps", "0", "--f16-steps", "0", "--mesh-steps", "0",
                         "--f32-steps", "0", "--noise-steps", "0"],
                        cwd=ROOT, capture_output=True, text=True, timeout=1500, env=env)

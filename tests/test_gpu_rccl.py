@@ -114,7 +114,7 @@ def test_bench_prints_its_contract_as_one_rccl_rank_under_the_launcher():
     N = 1: the rank forms an RCCL process group, barriers and the MAX-over-ranks reduction run, one JSON line comes out."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
-           "--warmup", "1", "--img-size", "64", "--n-qry", "4096", "--batch", "1", "--cpu-sample", "0", "--f16-steps", "0",
+           "--warmup", "1", "--img-size", "64", "--n-qry", "4096", "--batch", "1", "--full", "--cpu-sample", "0", "--f16-steps", "0",
            "--c4-steps", "0", "--mesh-steps", "0", "--ldm-steps", "0", "--train-steps", "1", "--gt-train-steps", "0",
            "--pmc", "0", "--f32-steps", "0", "--noise-steps", "0"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", S3D_FORCE_COLLECTIVES="1", OMP_NUM_THREADS="8")

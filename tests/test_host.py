@@ -147,6 +147,27 @@ def test_bench_dump_outputs_writes_float32_within_the_size_cap(tmp_path, monkeyp
     assert np.isin(s1, t.float().numpy()).all()
 
 
+def test_bench_runs_its_secondary_legs_with_full_only(capsys):
+    """bench.py without --full runs no secondary leg and refuses an option that would size one; --full runs each at its
+    FULL_LEGS size unless the command sizes it; --infer-only turns every leg off, --full or not."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    plain = bench.parse_args(["--steps", "3", "--warmup", "1"])
+    assert not plain.full and all(getattr(plain, k) == 0 for k in bench.FULL_LEGS)
+    assert bench.parse_args(["--cpu-sample", "0", "--pmc", "0"]).cpu_sample == 0
+    with pytest.raises(SystemExit) as e:
+        bench.parse_args(["--train-steps", "2"])
+    assert e.value.code == 2 and "--train-steps" in capsys.readouterr().err
+    full = bench.parse_args(["--full", "--ldm-steps", "1"])
+    assert full.full and full.ldm_steps == 1
+    assert all(getattr(full, k) == v for k, v in bench.FULL_LEGS.items() if k != "ldm_steps")
+    for argv in (["--infer-only"], ["--infer-only", "--full", "--train-steps", "2"]):
+        a = bench.parse_args(argv)
+        assert not a.full and all(getattr(a, k) == 0 for k in bench.FULL_LEGS)
+
+
 def test_generator3d_refuses_the_reference_dead_post_processing_branches():
     """reconstruct.py:205-240: with_normals / refinement_step / simplify_nfaces run through model.decode(p, c).logits under
     autograd w.r.t. the points — dead in the reference (its model has no decode()).  They must not be accepted and ignored."""

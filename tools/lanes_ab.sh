@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 for rep in 1 2; do
 for lanes in 1 2; do
-  S3D_DECODE_LANES=$lanes python bench.py --cpu-sample 0 --f16-steps 0 --f32-steps 0 --c4-steps 0 --mesh-steps 0 --ldm-steps 0 --train-steps 0 --gt-train-steps 0 --pmc 0 --noise-steps 40 --steps 30 --warmup 5 2>/dev/null | python -c "
+  S3D_DECODE_LANES=$lanes python bench.py --full --cpu-sample 0 --f16-steps 0 --f32-steps 0 --c4-steps 0 --mesh-steps 0 --ldm-steps 0 --train-steps 0 --gt-train-steps 0 --pmc 0 --noise-steps 40 --steps 30 --warmup 5 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.readline())
 w=r['white_noise']
