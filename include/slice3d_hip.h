@@ -286,7 +286,9 @@ int s3d_conv_pack(const float* w, const float* bias, int cout, int cin0, int cin
 /* prec (since version 110): S3D_PREC_F32 = exact fp32 MFMA; S3D_PREC_F16X3 = three f16 MFMAs per product (fp32-class);
  * S3D_PREC_F16 = the single-pass throughput mode (ONE f16 MFMA per product, operands rounded to f16 — not fp32-class; before
  * version 110 this value selected the exact fp32 path here).  Layers without an f16 weight image (channel counts that are not
- * multiples of 32: the stem) run the exact fp32 MFMA in every mode.  Any other value (S3D_PREC_BF16 included): S3D_E_ARG. */
+ * multiples of 32: the stem) run the exact fp32 MFMA in every mode.  Any other value (S3D_PREC_BF16 included): S3D_E_ARG.
+ * The pad channels of x0 / x1 (cin .. pad16(cin) - 1, here and in s3d_conv_strided_fwd) may hold any FINITE values: they meet
+ * zero weights and leave every output bit unchanged (a NaN or Inf there poisons the output). */
 int s3d_conv_fwd(const void* packed, const float* x0, const float* x1, const float* residual, float* out, int N,
                  int H, int W, int cout, int cin0, int cin1, int ks, int prec, void* workspace,
                  size_t workspace_bytes, void* stream);

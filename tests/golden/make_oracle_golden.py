@@ -39,6 +39,7 @@ from helpers import golden_digest, oracle_golden_path  # noqa: E402
 
 CASES = {
     "full256": test_gpu_parity._oc_full256,
+    "full256_edges": test_gpu_parity._oc_full256_edges,
     "white_s256_q6000": test_gpu_parity._oc_white,
     "sweep24": test_gpu_parity._oc_sweep,
     "gt_white_s128_q5000": test_gpu_gt._oc_gt_white,

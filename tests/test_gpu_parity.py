@@ -95,6 +95,40 @@ def _oc_full256():
     return {"sdf_sub": sub.numpy(), "rec_probe": _probe(rec).contiguous().numpy(), "c4_sdf": c4.reshape(-1).numpy()}
 
 
+EDGE_ROWS, EDGE_COLS = (0, 7, 8, 255), (0, 15, 16, 255)   # image borders and the 8-row / 16-column seams of the tiled 3x3 kernel
+
+
+def _edge_lines(rec):
+    """slices_rec (..., 256, 256) on the rows EDGE_ROWS x all columns and the columns EDGE_COLS x all rows."""
+    return rec[..., list(EDGE_ROWS), :].contiguous(), rec[..., :, list(EDGE_COLS)].contiguous()
+
+
+def _ring_channels(c):
+    return [0, c // 3, (2 * c) // 3, c - 1]
+
+
+def _border_ring(f):
+    """First and last row and column of a pyramid level (B, C, H, W) for four fixed channels -> (B, 4, 2W + 2(H - 2))."""
+    s = f[:, _ring_channels(f.shape[1])]
+    return torch.cat([s[..., 0, :], s[..., -1, :], s[..., 1:-1, 0], s[..., 1:-1, -1]], -1).contiguous()
+
+
+def _oc_full256_edges():
+    """Oracle at the inputs and weights of _oc_full256 (seed 2024): slices_rec on the image borders and the tiled kernel's
+    seams (_edge_lines), which the pixel probe never reaches, and the border ring of every pyramid level (_border_ring)."""
+    from oracle import ref_cpu
+    from slice3d_amd.synth import make_feed_dict
+    sd = seeded_sd_from_shapes(_shapes(12))
+    fd = make_feed_dict(1, 256, 100000, 12, seed=2024, with_slices=False)
+    with torch.no_grad():
+        feats, rec = ref_cpu.unet_forward(sd, fd["img_input"], 12)
+    rows, cols = _edge_lines(rec)
+    z = {"rec_rows": rows.numpy(), "rec_cols": cols.numpy()}
+    for l, f in enumerate(feats):
+        z["ring%d" % l] = _border_ring(f).numpy()
+    return z
+
+
 def _oc_white():
     """fp32 and fp64 oracle on SURVEY 8(d)'s white-noise inputs (seed 1234, 256^2, 6000 queries)."""
     from oracle import ref_cpu
@@ -242,6 +276,31 @@ def test_full_size_256_matches_oracle(prec):
     rec = out["slices_rec"].cpu().view(12, 3, 256, 256)
     assert torch.isfinite(rec).all()
     assert (_probe(rec) - torch.from_numpy(z["rec_probe"])).abs().max() < TOL
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_full_size_256_edges_match_oracle(prec):
+    """The same 256^2 x 12-slice image: slices_rec on rows 0, 7, 8, 255 and columns 0, 15, 16, 255 (image borders and the
+    tiled 3x3 kernel's seams, none of them on the pixel probe) and the border ring of all five pyramid levels (committed
+    outputs: _oc_full256_edges)."""
+    from slice3d_amd.synth import make_feed_dict
+    model = get_model(12, "test", prec)
+    fd = make_feed_dict(1, 256, 16, 12, seed=2024, with_slices=False)
+    feats, rec = model.slices_generator(fd["img_input"].cuda())
+    z = _oracle_case("full256_edges", _oc_full256_edges)
+    rec = rec.cpu().view(12, 3, 256, 256)
+    rows, cols = _edge_lines(rec)
+    for got, key in ((rows, "rec_rows"), (cols, "rec_cols")):
+        assert torch.isfinite(got).all(), key
+        err = float((got - torch.from_numpy(z[key])).abs().max())
+        assert err < TOL, (key, err)
+    assert len(feats) == 5
+    for l, f in enumerate(feats):
+        ring = _border_ring(f.cpu())
+        ref = torch.from_numpy(z["ring%d" % l])
+        assert ring.shape == ref.shape, (l, ring.shape, ref.shape)
+        err = float((ring - ref).abs().max())
+        assert err < TOL * max(1.0, float(ref.abs().max())), (l, err)
 
 
 @pytest.mark.parametrize("prec", PRECS)
