@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define S3D_VERSION 116          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd */
+#define S3D_VERSION 117          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample) */
 #define S3D_E_ARG (-1)           /* bad argument / unsupported shape */
 #define S3D_E_WORKSPACE (-2)     /* workspace or packed-weight buffer too small */
 
@@ -585,6 +585,49 @@ int s3d_mc_dev_count(const void* grid, int is_f64, int nx, int ny, int nz, int p
                      void* workspace, size_t workspace_bytes, long* n_vertices, long* n_triangles, void* stream);
 int s3d_mc_dev_emit(const void* grid, int is_f64, int nx, int ny, int nz, int pad, double pad_value, double iso,
                     void* workspace, size_t workspace_bytes, double* vertices, long long* triangles, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh evaluation — the scores of reg_slices/src/utils_eval.py:1-109 on the device.
+ * Meshes enter as s3d_mc_dev_emit leaves them: vertices (V,3) float64, faces (F,3) int64, device buffers.
+ * ------------------------------------------------------------------------------------------- */
+/* Point-in-mesh: replaces check_mesh_contains (src_convonet/utils/libmesh/inside_mesh.py:5-139) and its compiled cell
+ * hash (libmesh/triangle_hash.pyx:10-88), bit for bit.  float64 throughout: the bbox of the vertices the faces
+ * reference, scale = (res-1)/(bmax-bmin), translate = 0.5 - scale*bmin, every coordinate scale*x + translate (float32
+ * points widened first); each triangle is listed in every cell res*x + y of its (int)-truncated xy box clamped to
+ * [0, res-1]; a point outside [0, res]^3, or whose (int) x or y is res, is outside; otherwise it counts the triangles of
+ * its cell that pass the strict 2-D test (det == 0 skipped) at depth >= pz*|n_z| and at depth < pz*|n_z| (|n_z| == 0:
+ * neither) and is inside when both counts are odd.  A mesh whose bbox is flat on an axis (or that has no face) contains
+ * no point, as the reference's inf / NaN rescale amounts to.
+ * Three calls on one workspace (res = hash_resolution, 2..8192):
+ *   build: bbox, rescale, cell counts and offsets; returns the entry count (64-bit) through one stream synchronisation.
+ *          S3D_E_ARG when a face indexes a vertex outside [0, n_vertices).
+ *   fill:  the cell lists into entries[n_entries] (int32 face indices, caller-owned).
+ *   query: inside[n_points] (uint8 0/1) for points (n,3) float32 (is_f64 = 0) or float64; n_disagree (optional, one
+ *          uint64) = the points inside the bbox whose two parities differ (the reference prints a warning for them).
+ *          Any number of queries may follow one build + fill. */
+size_t s3d_mesh_contains_workspace_bytes(long n_faces, int hash_resolution);
+int s3d_mesh_contains_build(const double* vertices, long n_vertices, const long long* faces, long n_faces,
+                            int hash_resolution, void* workspace, size_t workspace_bytes, long* n_entries, void* stream);
+int s3d_mesh_contains_fill(long n_faces, int hash_resolution, void* workspace, size_t workspace_bytes, int* entries,
+                           long n_entries, void* stream);
+int s3d_mesh_contains_query(long n_faces, int hash_resolution, const void* workspace, size_t workspace_bytes,
+                            const int* entries, long n_entries, const void* points, int is_f64, long n_points,
+                            unsigned char* inside, unsigned long long* n_disagree, void* stream);
+/* Exact nearest neighbour (what utils_eval.points_dist gets from cKDTree.query, k = 1): d2[i] = min_j |a_i - b_j|^2 in
+ * fp32 from coordinate differences (dx*dx + dy*dy + dz*dz, no MFMA, no |a|^2 - 2a.b + |b|^2 expansion), idx[i] = its j
+ * (optional, NULL to skip), the lowest j on ties.  a (na,3), b (nb,3) float32.  nb == 0: S3D_E_ARG; na == 0 launches
+ * nothing.  workspace: s3d_nn_workspace_bytes(na). */
+size_t s3d_nn_workspace_bytes(long na);
+int s3d_nn_sqdist(const float* a, long na, const float* b, long nb, void* workspace, size_t workspace_bytes, float* d2,
+                  long long* idx, void* stream);
+/* Area-weighted surface sampling: float64 face areas, their inclusive prefix sum, sample i takes the first face whose
+ * cdf > u*total and the point (1-sqrt(r1))*A + sqrt(r1)*(1-r2)*B + sqrt(r1)*r2*C, with u, r1, r2 hashed from (seed, i)
+ * (independent of the launch geometry).  Zero-area faces are never chosen.  -> points (n,3) float32, face_idx (n)
+ * int64; a mesh of zero total area gives NaN points and face -1.  workspace: s3d_surface_sample_workspace_bytes. */
+size_t s3d_surface_sample_workspace_bytes(long n_faces);
+int s3d_surface_sample(const double* vertices, long n_vertices, const long long* faces, long n_faces, long n_samples,
+                       unsigned long long seed, void* workspace, size_t workspace_bytes, float* points,
+                       long long* face_idx, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Dataset staging on the device — the per-sample tensor work of Slice3DDataset.__getitem__
