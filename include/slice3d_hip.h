@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define S3D_VERSION 117          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample) */
+#define S3D_VERSION 118          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding */
 #define S3D_E_ARG (-1)           /* bad argument / unsupported shape */
 #define S3D_E_WORKSPACE (-2)     /* workspace or packed-weight buffer too small */
 
@@ -628,6 +628,51 @@ size_t s3d_surface_sample_workspace_bytes(long n_faces);
 int s3d_surface_sample(const double* vertices, long n_vertices, const long long* faces, long n_faces, long n_samples,
                        unsigned long long seed, void* workspace, size_t workspace_bytes, float* points,
                        long long* face_idx, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Signed-distance targets from a mesh (csrc/mesh_sdf.hip) — what 02_sdfs/<shape>.npy is made from.  No counterpart in the
+ * reference's tree (its README:49 names an external script; reg_slices/src/datasets.py:142-148 is the consumer that fixes
+ * the file format).  Same conventions as the mesh evaluation above: vertices (V,3) float64 and faces (F,3) int64 device
+ * buffers, points (n,3) float32 (is_f64 = 0) or float64, caller-owned workspace, nothing allocated or kept by the library;
+ * S3D_E_ARG with a message when a face indexes a vertex outside [0, n_vertices).
+ * ------------------------------------------------------------------------------------------- */
+/* Exact unsigned distance: dist[i] = min over ALL faces of the distance from point i to the triangle, float64 (float32
+ * points widened first).  A zero-area face is the segment or point it degenerates to: never NaN, never skipped.
+ *   build: a grid of resolution^3 cells (1..256 per axis; one cell on an axis where the box is flat) over the bounding box
+ *          of the vertices the faces reference; every triangle is counted in every cell its box overlaps; offsets by a
+ *          scan; per cell the Chebyshev distance to the nearest occupied cell.  Returns the entry count (64-bit) through
+ *          one stream synchronisation.  n_faces == 0: S3D_E_ARG.
+ *   fill:  the cell lists into entries[n_entries] (int32 face indices, caller-owned).
+ *   query: cells are visited in shells of growing Chebyshev radius around the point's clamped cell, from the first shell
+ *          that holds an occupied cell, until the lower bound of everything beyond the last shell exceeds the best
+ *          distance; points outside the grid, however far, are legal and exact.  Every loop is bounded by the grid size.
+ *          dist (n) float64; face (n) int64 (optional, NULL to skip): the face that attains it; n_tests (optional, one
+ *          uint64): the point-triangle tests performed.  n_points == 0 launches nothing.  Any number of queries may
+ *          follow one build + fill.
+ * Determinism: a face's squared distance to a point is one fixed operation sequence; dist is the square root of the
+ * minimum of those values and face the lowest index among the faces that attain it bit for bit — the same bits from run to
+ * run, for every resolution, and for float32 points and their widened copies.  No atomics touch the result. */
+size_t s3d_mesh_dist_workspace_bytes(long n_faces, int resolution);
+int s3d_mesh_dist_build(const double* vertices, long n_vertices, const long long* faces, long n_faces, int resolution,
+                        void* workspace, size_t workspace_bytes, long* n_entries, void* stream);
+int s3d_mesh_dist_fill(long n_faces, int resolution, void* workspace, size_t workspace_bytes, int* entries,
+                       long n_entries, void* stream);
+int s3d_mesh_dist_query(long n_faces, int resolution, const void* workspace, size_t workspace_bytes, const int* entries,
+                        long n_entries, const void* points, int is_f64, long n_points, double* dist, long long* face,
+                        unsigned long long* n_tests, void* stream);
+/* Generalised winding number: w[i] = sum over faces of Omega_f(p_i) / 4 pi, Omega_f = 2 atan2(det[a b c], |a||b||c| +
+ * (a.b)|c| + (b.c)|a| + (c.a)|b|) with a, b, c the face's vertices relative to the point (Van Oosterom & Strackee),
+ * float64.  +1 inside a closed mesh whose faces are counter-clockwise seen from outside, 0 outside, in between near a
+ * hole.  A point on a face's plane inside the face gets that face's limit value as the formula gives it (+-2 pi or 0), a
+ * point on a vertex 0 from the faces around it; no NaN.  Faces are summed in fixed chunks (a function of n_faces alone) in
+ * face order and the chunk sums in chunk order, so w is bit-reproducible whatever n_splits — the number of blocks the
+ * chunks are dealt to (0: chosen from n_points so that few points still fill the chip).  The faces are validated by a
+ * kernel of their own (one stream synchronisation) before anything dereferences them.  n_faces == 0: S3D_E_ARG;
+ * n_points == 0 launches nothing.  workspace: s3d_mesh_winding_workspace_bytes(n_faces, n_points). */
+size_t s3d_mesh_winding_workspace_bytes(long n_faces, long n_points);
+int s3d_mesh_winding(const double* vertices, long n_vertices, const long long* faces, long n_faces, const void* points,
+                     int is_f64, long n_points, int n_splits, void* workspace, size_t workspace_bytes, double* w,
+                     void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Dataset staging on the device — the per-sample tensor work of Slice3DDataset.__getitem__

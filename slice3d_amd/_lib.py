@@ -205,6 +205,12 @@ SYMBOLS = {
     "s3d_nn_sqdist": (_i, [_vp, _l, _vp, _l, _vp, _sz, _vp, _vp, _vp]),
     "s3d_surface_sample_workspace_bytes": (_sz, [_l]),
     "s3d_surface_sample": (_i, [_vp, _l, _vp, _l, _l, C.c_ulonglong, _vp, _sz, _vp, _vp, _vp]),
+    "s3d_mesh_dist_workspace_bytes": (_sz, [_l, _i]),
+    "s3d_mesh_dist_build": (_i, [_vp, _l, _vp, _l, _i, _vp, _sz, C.POINTER(C.c_long), _vp]),
+    "s3d_mesh_dist_fill": (_i, [_l, _i, _vp, _sz, _vp, _l, _vp]),
+    "s3d_mesh_dist_query": (_i, [_l, _i, _vp, _sz, _vp, _l, _vp, _i, _l, _vp, _vp, _vp, _vp]),
+    "s3d_mesh_winding_workspace_bytes": (_sz, [_l, _l]),
+    "s3d_mesh_winding": (_i, [_vp, _l, _vp, _l, _vp, _i, _l, _i, _vp, _sz, _vp, _vp]),
     "s3d_dataset_images_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "s3d_dataset_points_fwd": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _vp]),
     "s3d_nchw_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
