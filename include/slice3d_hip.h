@@ -361,6 +361,7 @@ int s3d_small_linear_fwd(const float* x, const float* w, const float* b, float* 
 int s3d_timestep_embedding_fwd(const float* t, float* out, int N, int dim, float max_period, void* stream);
 /* out = a + b (c_fmaps injection, openaimodel.py:735-746) */
 int s3d_add_fwd(const float* a, const float* b, float* out, long n, void* stream);
+/* in (n,c,h,w) -> out (n,h,w,cpad), cpad >= c a multiple of 4; the pad channels c .. cpad are written as +0.0 */
 int s3d_nchw_to_nhwc_pad(const float* in, float* out, int n, int c, int h, int w, int cpad, void* stream);
 /* out (N,H,W,C) = a (N,H,W,C) + b (N,C,H,W): the same injection with the feature map taken as the reference hands it over (version 115) */
 int s3d_add_nchw_fwd(const float* a, const float* b, float* out, int n, int c, int h, int w, void* stream);

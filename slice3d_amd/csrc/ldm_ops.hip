@@ -96,17 +96,19 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnSrc src, int HW, 
 // Round 4: the same partial moments from ONE coalesced pass.  gn_stats_kernel above walks a group's C/32 channels of every
 // pixel (24-byte runs at a C*4-byte stride) twice; the one-launch gn_fused_kernel below reads the same way with only
 // N*32 workgroups — 15 / 21 us for a 3 MB map.  Here a workgroup owns a slab of pixels of one image with ALL channels:
-// thread = (pixel lane, channel quad), 16-byte loads along the channel axis, shifted sums sum(x - k), sum((x - k)^2) about
-// the slab's first pixel k[c] (the cancellation of E[d^2] - E[d]^2 is then of the size (mean - k)^2 / var of a channel
-// inside one slab), per-channel totals through LDS adds, then one thread per group folds its C/32 channels into
+// thread = (pixel lane, channel quad), 16-byte loads along the channel axis.  A thread keeps (count, mean, M2) of its rows
+// per channel: four rows in flight give a chunk's mean and centred squares exactly as a two-pass sum would, and the chunk is
+// merged into the running moments with Chan's formula (its weights depend on the chunk index alone).  No sum is taken about
+// a value picked from the data, so no pixel of the slab - an outlier in its first row included - decides the rounding error
+// (the earlier form summed x - k and (x - k)^2 about the slab's first pixel k and lost (mean - k)^2 / var of precision).
+// The lanes' moments are merged in lane order through LDS, then one thread per group folds its C/32 channels into
 // (count, mean, M2) — the partial gn_apply_kernel merges with Chan's formula, as before.
 __global__ __launch_bounds__(1024) void gn_stats_rows_kernel(const GnSrc src, int HW, int C, int groups,
                                                              float* __restrict__ part) {
-    extern __shared__ float s_g[];          // k[C] | sum1[C] | sum2[C] | per-lane partials [lanes][2][C]
-    float* s_k = s_g;
-    float* s_1 = s_g + C;
-    float* s_2 = s_g + 2 * C;
-    float* s_p = s_g + 3 * C;
+    extern __shared__ float s_g[];          // mean[C] | M2[C] | per-lane (mean, M2) [lanes][2][C]
+    float* s_1 = s_g;
+    float* s_2 = s_g + C;
+    float* s_p = s_g + 2 * C;
     const int sl = blockIdx.x % GN_SLICES, n = blockIdx.x / GN_SLICES;
     const int p0 = (int)((long)HW * sl / GN_SLICES), p1 = (int)((long)HW * (sl + 1) / GN_SLICES);
     const int cq = C >> 2, lanes = 1024 / cq;            // pixel lanes per pass (C <= 4096)
@@ -118,52 +120,60 @@ __global__ __launch_bounds__(1024) void gn_stats_rows_kernel(const GnSrc src, in
         return ld4(src.x1 + q * (C - src.C0) + (c - src.C0));
     };
     if (pr < lanes) {
-        f32x4 a1 = zero4(), a2 = zero4();
-        if (p1 > p0) {
-            const f32x4 k = row(p0);
-            int p = p0 + pr;
-            for (; p + 3 * lanes < p1; p += 4 * lanes) {   // four rows in flight (the loop is latency-bound otherwise)
-                const f32x4 r0 = row(p), r1 = row(p + lanes), r2 = row(p + 2 * lanes), r3 = row(p + 3 * lanes);
-                const f32x4 d0 = r0 - k, d1 = r1 - k, d2 = r2 - k, d3 = r3 - k;
-                a1 += (d0 + d1) + (d2 + d3);
-                a2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-            }
-            for (; p < p1; p += lanes) {
-                const f32x4 d = row(p) - k;
-                a1 += d;
-                a2 += d * d;
-            }
-            if (pr == 0) st4(s_k + c, k);
-        } else if (pr == 0) {
-            st4(s_k + c, zero4());
+        f32x4 mean = zero4(), m2 = zero4();
+        float cnt = 0.f;
+        int p = p0 + pr;
+        for (; p + 3 * lanes < p1; p += 4 * lanes) {   // four rows in flight (the loop is latency-bound otherwise)
+            const f32x4 r0 = row(p), r1 = row(p + lanes), r2 = row(p + 2 * lanes), r3 = row(p + 3 * lanes);
+            const f32x4 cm = ((r0 + r1) + (r2 + r3)) * 0.25f;
+            const f32x4 d0 = r0 - cm, d1 = r1 - cm, d2 = r2 - cm, d3 = r3 - cm;
+            const f32x4 cs = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+            const float tot = cnt + 4.f, w = 4.f / tot;
+            const f32x4 d = cm - mean;
+            mean += d * w;
+            m2 += cs + d * d * (cnt * w);
+            cnt = tot;
         }
-        st4(s_p + (size_t)(2 * pr) * C + c, a1);
-        st4(s_p + (size_t)(2 * pr + 1) * C + c, a2);
+        for (; p < p1; p += lanes) {   // Welford's update for the rows left over
+            const f32x4 r = row(p);
+            cnt += 1.f;
+            const f32x4 d = r - mean;
+            mean += d * (1.f / cnt);
+            m2 += d * (r - mean);
+        }
+        st4(s_p + (size_t)(2 * pr) * C + c, mean);
+        st4(s_p + (size_t)(2 * pr + 1) * C + c, m2);
     }
     __syncthreads();
-    if (pr == 0) {   // the pixel lanes' partials in a fixed order (no atomics: the result is bit-reproducible)
-        f32x4 t1 = zero4(), t2 = zero4();
-        for (int l = 0; l < lanes; ++l) {
-            t1 += ld4(s_p + (size_t)(2 * l) * C + c);
-            t2 += ld4(s_p + (size_t)(2 * l + 1) * C + c);
+    const int np = p1 - p0;
+    if (pr == 0) {   // the pixel lanes' moments in a fixed order (no atomics: the result is bit-reproducible)
+        f32x4 mean = zero4(), m2 = zero4();
+        float cnt = 0.f;
+        for (int l = 0; l < lanes && l < np; ++l) {
+            const float nl = (float)((np - l + lanes - 1) / lanes);   // rows lane l has seen
+            const f32x4 ml = ld4(s_p + (size_t)(2 * l) * C + c), ql = ld4(s_p + (size_t)(2 * l + 1) * C + c);
+            const float tot = cnt + nl, w = nl / tot;
+            const f32x4 d = ml - mean;
+            mean += d * w;
+            m2 += ql + d * d * (cnt * w);
+            cnt = tot;
         }
-        st4(s_1 + c, t1);
-        st4(s_2 + c, t2);
+        st4(s_1 + c, mean);
+        st4(s_2 + c, m2);
     }
     __syncthreads();
     if ((int)threadIdx.x < groups) {
         const int g = threadIdx.x, cpg = C / groups;
-        const float np = (float)(p1 - p0);
         float mean_g = 0.f;
-        for (int j = 0; j < cpg; ++j) mean_g += s_k[g * cpg + j] + s_1[g * cpg + j] / fmaxf(np, 1.f);
+        for (int j = 0; j < cpg; ++j) mean_g += s_1[g * cpg + j];
         mean_g /= (float)cpg;
         float m2 = 0.f;
         for (int j = 0; j < cpg; ++j) {
-            const float s1 = s_1[g * cpg + j], mc = s_k[g * cpg + j] + s1 / fmaxf(np, 1.f);
-            m2 += (s_2[g * cpg + j] - s1 * s1 / fmaxf(np, 1.f)) + np * (mc - mean_g) * (mc - mean_g);
+            const float mc = s_1[g * cpg + j];
+            m2 += s_2[g * cpg + j] + (float)np * (mc - mean_g) * (mc - mean_g);
         }
         float* o = part + 3 * ((size_t)(n * groups + g) * GN_SLICES + sl);
-        o[0] = np * (float)cpg;
+        o[0] = (float)np * (float)cpg;
         o[1] = mean_g;
         o[2] = fmaxf(m2, 0.f);
     }
@@ -339,8 +349,8 @@ __global__ __launch_bounds__(1024) void gn_fused_kernel(const GnSrc src, const f
     if (table) {   // no normalised output: this group's rows of the affine table y = x * A + B (gamma / beta / FiLM folded) that the
                    // consuming convolution applies while it stages its input (ConvGn, conv.h)
         const float rs = 1.f / sqrtf(m2 / (float)total + eps);
-        if ((int)threadIdx.x < cpg) {
-            const int c = gidx * cpg + threadIdx.x;
+        for (int j = threadIdx.x; j < cpg; j += 1024) {   // (C / groups may exceed the workgroup: 2048 channels in one group)
+            const int c = gidx * cpg + j;
             float A = rs * gamma[c], B = beta[c] - mean * A;
             if (film) {
                 const float sc = 1.f + film[(long)n * film_ld + c];
@@ -402,9 +412,9 @@ int launch_group_norm(const float* x, const float* gamma, const float* beta, con
         }
     }
     S3D_CHECK_ARG((size_t)N * groups * 2 * sizeof(float) <= 48 * 1024, "group_norm: N*groups %d too large", N * groups);
-    if (C <= 2048 && groups <= 1024)   // (LDS: 7 C floats) coalesced one-pass partial moments (all channels of a pixel slab per workgroup)
+    if (C <= 2048 && groups <= 1024)   // (LDS: 6 C floats) coalesced one-pass partial moments (all channels of a pixel slab per workgroup)
         hipLaunchKernelGGL(gn_stats_rows_kernel, dim3(N * GN_SLICES), dim3(1024),
-                           (size_t)(3 * C + 2 * (1024 / (C / 4)) * C) * sizeof(float), stream, src, HW, C, groups, stats);
+                           (size_t)(2 * C + 2 * (1024 / (C / 4)) * C) * sizeof(float), stream, src, HW, C, groups, stats);
     else {
         S3D_CHECK_ARG(!part, "group_norm: partial-sum source with C = %d > 2048", C);
         hipLaunchKernelGGL(gn_stats_kernel, dim3(N * groups * GN_SLICES), dim3(256), 0, stream, src, HW, C, groups, stats);
