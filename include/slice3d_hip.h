@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define S3D_VERSION 118          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding */
+#define S3D_VERSION 119          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding; 119: s3d_mesh_render_* */
 #define S3D_E_ARG (-1)           /* bad argument / unsupported shape */
 #define S3D_E_WORKSPACE (-2)     /* workspace or packed-weight buffer too small */
 
@@ -674,6 +674,43 @@ size_t s3d_mesh_winding_workspace_bytes(long n_faces, long n_points);
 int s3d_mesh_winding(const double* vertices, long n_vertices, const long long* faces, long n_faces, const void* points,
                      int is_f64, long n_points, int n_splits, void* workspace, size_t workspace_bytes, double* w,
                      void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Rendering a mesh into the dataset's images (mesh_render.hip; slice3d_amd/mesh_render.py, render_slices/gen_dataset.py):
+ * the RGBA input view and the RGBA images of the 12 slabs (four per axis) that the reference renders with Blender
+ * (render_slices/blender_script_input.py, blender_script_slices.py).  One camera per call.  Mesh conventions as above.
+ *
+ * camera: 26 float64 on the HOST: R (3x3, row-major), distance, scale, t[3], M (3x4, row-major).  A vertex v becomes
+ * c = (v * scale + t) R (x right, y down, z away from the camera) and p = c + (0, 0, distance); the pinhole has focal
+ * length 35/32 image widths, pixel row 0 at the top.  Each pixel holds samples x samples rays (samples = 1, 2 or 4)
+ * d = ((u - 0.5) / f, (v - 0.5) / f, 1), u = (i + (a + 0.5) / samples) / size.  A ray hits the face (a, b, c) iff its normal
+ * n = (b - a) x (c - a) is not zero, d.(b x c), d.(c x a), d.(a x b) are all >= 0 or all <= 0 and not all zero, and
+ * s = (a.n) / (d.n) > 0; the nearest hit has the smallest s, the lowest face index on equal s.  The hit point
+ * P = s d - (0, 0, distance) has slab coordinates M [P, 1]; per axis the slab index is the count of i in {1, 2, 3} with
+ * coordinate >= lo + (hi - lo) / 4 * i, lo / hi over the vertices the faces reference (0 where hi == lo).  Image 0 is the
+ * nearest hit, images 1 + 4 axis + k the nearest hit among the hits of slab k of the axis: the hollow surface inside it.
+ *   build:  transforms, slab bounds, the conservative range of pixel tiles of every face (a face with a vertex at
+ *           p_z <= 0 goes to every tile), entries per tile and their scan.  Returns the entry count through one stream
+ *           synchronisation.  S3D_E_ARG for size outside 1..1024, samples not in {1, 2, 4}, tile < 1 or tile * samples > 32.
+ *   fill:   the tile lists into entries[n_entries] (int32 face indices, caller-owned).
+ *   render: one workgroup per tile, one thread per sample; face (13, size * samples, size * samples) int32, -1 = miss;
+ *           depth (same shape, float64 s, +inf = miss; optional); rgba (13, size, size, 4) uint8 (optional): alpha =
+ *           round(255 * covered / samples^2), straight; rgb = round(255 * mean over the covered samples of albedo *
+ *           (0.5 + 0.5 |n.d| / (|n| |d|))), albedo 0.8 or, on image 0 with vertex_colors (V, 3) float64, the mean of the
+ *           face's three vertex colours; (0, 0, 0, 0) where nothing is covered.  n_tests (optional, one uint64): ray-face
+ *           tests performed.
+ * `tile` (pixels per tile edge) changes the speed only: every output is the same bits for every value, and from run to run.
+ * ------------------------------------------------------------------------------------------- */
+size_t s3d_mesh_render_workspace_bytes(long n_vertices, long n_faces, int size, int samples, int tile);
+int s3d_mesh_render_build(const double* vertices, long n_vertices, const long long* faces, long n_faces,
+                          const double* camera, int size, int samples, int tile, void* workspace, size_t workspace_bytes,
+                          long* n_entries, void* stream);
+int s3d_mesh_render_fill(long n_vertices, long n_faces, int size, int samples, int tile, void* workspace,
+                         size_t workspace_bytes, int* entries, long n_entries, void* stream);
+int s3d_mesh_render_render(long n_vertices, const long long* faces, long n_faces, int size, int samples, int tile,
+                           const void* workspace, size_t workspace_bytes, const int* entries, long n_entries,
+                           const double* vertex_colors, double* depth, int* face, unsigned char* rgba,
+                           unsigned long long* n_tests, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Dataset staging on the device — the per-sample tensor work of Slice3DDataset.__getitem__
