@@ -86,7 +86,29 @@ struct TrainBufs {
     size_t partial_floats;
     float* cpartial;         // column / scalar reduction partials
     float* vec;              // small vectors (colsum outputs etc.)
+    float* fwd_losses;       // [loss_pred, loss_img, loss_vgg, acc] of a forward-only step: the end of vec, beyond its small-vector uses
 };
+
+// every size a training step derives from (B, S, Q, ns), computed once: the plans and the run read it from here
+struct StepDims {
+    int B, S, ns;
+    long Q;
+    int Nd, Tn, r5;          // slice images B * ns, tokens per query ns + 1, side of the coarsest feature map S / 16
+    long gpb, G;             // query groups (of S3D_GROUP) per object / in all
+    long rows, rows0;        // token rows G * Tn * S3D_GROUP, token-0 rows G * S3D_GROUP
+    long nsdf, nimg;         // elements of sdf_pred (B,Q) and of slices_rec (Nd,3,S,S)
+};
+static StepDims step_dims(int B, int S, long Q, int ns) {
+    StepDims d;
+    d.B = B; d.S = S; d.ns = ns; d.Q = Q;
+    d.Nd = B * ns; d.Tn = ns + 1; d.r5 = S / 16;
+    d.gpb = (Q + S3D_GROUP - 1) / S3D_GROUP; d.G = d.gpb * B;
+    d.rows = d.G * d.Tn * S3D_GROUP; d.rows0 = d.G * S3D_GROUP;
+    d.nsdf = (long)B * Q; d.nimg = (long)d.Nd * 3 * S * S;
+    return d;
+}
+static const int kLatC[5] = {512, 256, 128, 64, 32};   // channels of the U-Net's feature levels F[0..4]
+static const int kFcsCol[3] = {0, 512, 768};            // first column of fc_s.weight that the folded projection of level l uses
 
 static FragW frag_alloc(Arena& A, int n, int k) {
     FragW f;
@@ -98,8 +120,8 @@ static FragW frag_alloc(Arena& A, int n, int k) {
 }
 
 // VGG16-BN encoder buffers for n_img input images (shared by the two regression models)
-static void plan_enc(Arena& A, int n_img, int S, TrainBufs& T) {
-    const size_t px = (size_t)n_img * S * S;
+static void plan_enc(Arena& A, const StepDims& d, int n_img, TrainBufs& T) {
+    const size_t px = (size_t)n_img * d.S * d.S;
     T.in16 = A.take(px * 16);
     T.ein[0] = T.in16;
     for (int i = 0; i < 13; ++i) {
@@ -117,10 +139,10 @@ static void plan_enc(Arena& A, int n_img, int S, TrainBufs& T) {
 }
 
 // transformer decoder buffers (DecoderTrain) for B objects x Q queries x (ns + 1) tokens
-static void plan_dec(Arena& A, int B, long Q, int ns, TrainBufs& T) {
-    const long gpb = (Q + S3D_GROUP - 1) / S3D_GROUP, G = gpb * B;
-    const int Tn = ns + 1;
-    const size_t rows = (size_t)G * Tn * S3D_GROUP, rows0 = (size_t)G * S3D_GROUP;
+static void plan_dec(Arena& A, const StepDims& d, TrainBufs& T) {
+    const int B = d.B;
+    const long Q = d.Q;
+    const size_t rows = (size_t)d.rows, rows0 = (size_t)d.rows0;
     T.X0 = A.take(rows * 128);
     T.perm = (int*)A.take((size_t)B * Q + 4);
     T.sortws = (int*)A.take(query_sort_ws_ints(B, Q) + 4);
@@ -175,22 +197,22 @@ static void plan_shared(Arena& A, TrainBufs& T) {
     T.partial = A.take(T.partial_floats);
     T.cpartial = A.take((size_t)2 * CS_CHUNKS_MAX * 2048 + 4096);
     T.vec = A.take(8192);
+    T.fwd_losses = T.vec ? T.vec + 8000 : nullptr;
 }
 
-static void plan_train(Arena& A, int B, int S, long Q, int ns, TrainBufs& T) {
-    const int Nd = B * ns;
-    plan_enc(A, B, S, T);
-    const int lc[5] = {512, 256, 128, 64, 32};
+static void plan_train(Arena& A, const StepDims& d, TrainBufs& T) {
+    const int B = d.B, S = d.S, ns = d.ns, Nd = d.Nd;
+    plan_enc(A, d, B, T);
     for (int l = 0; l < 5; ++l) {
-        const size_t r = (size_t)(S / 16) << l;
-        T.F[l] = A.take((size_t)Nd * r * r * lc[l]);
-        T.dF[l] = A.take((size_t)Nd * r * r * lc[l]);
+        const size_t r = (size_t)d.r5 << l;
+        T.F[l] = A.take((size_t)Nd * r * r * kLatC[l]);
+        T.dF[l] = A.take((size_t)Nd * r * r * kLatC[l]);
     }
     T.w_transc = frag_alloc(A, 512, 640);
     T.w_transc_d = frag_alloc(A, 512, 512);
     for (int i = 0; i < 4; ++i) {
         const int C = kUpC[i], Ct = C / 2;
-        const size_t ro = (size_t)(S / 16) << (i + 1);
+        const size_t ro = (size_t)d.r5 << (i + 1);
         T.proj[i] = A.take((size_t)B * ro * ro * Ct);
         T.up[i] = A.take((size_t)Nd * ro * ro * Ct);
         T.z1[i] = A.take((size_t)Nd * ro * ro * Ct);
@@ -229,21 +251,19 @@ static void plan_train(Arena& A, int B, int S, long Q, int ns, TrainBufs& T) {
     T.w_vggZ = frag_alloc(A, 27, 64);
     T.vgA = A.take(vpx / 2 * 64); T.vgB = A.take(vpx / 2 * 64);
     // decoder
-    const long gpb = (Q + S3D_GROUP - 1) / S3D_GROUP, G = gpb * B;
-    const int Tn = ns + 1;
-    const size_t rows = (size_t)G * Tn * S3D_GROUP, rows0 = (size_t)G * S3D_GROUP;
+    const size_t rows = (size_t)d.rows, rows0 = (size_t)d.rows0;
     T.head_packed = A.take(head_layout().total);
     for (int l = 0; l < 3; ++l) {
-        const size_t r = (size_t)(S / 16) << l;
+        const size_t r = (size_t)d.r5 << l;
         T.lat_proj[l] = A.take((size_t)Nd * r * r * 128);
         T.dlat_proj[l] = A.take((size_t)Nd * r * r * 128);
-        T.w_projT[l] = frag_alloc(A, lc[l], 128);
+        T.w_projT[l] = frag_alloc(A, kLatC[l], 128);
     }
     T.ws34_t = A.take(96 * 128);
     T.ws34_t16 = A.take(96 * 128);
     T.raw34 = A.take(rows * 96);
     T.qrot4 = A.take(rows0 * 4);
-    plan_dec(A, B, Q, ns, T);
+    plan_dec(A, d, T);
     {
         const size_t n = sample_bwd_partial_floats(S, B, ns);
         T.sb_partial = n ? A.take(n) : nullptr;
@@ -254,7 +274,7 @@ static void plan_train(Arena& A, int B, int S, long Q, int ns, TrainBufs& T) {
 extern "C" size_t s3d_train_workspace_bytes(int batch, int size, long n_qry, int n_slices) {
     Arena A{nullptr, 0};
     TrainBufs T;
-    plan_train(A, batch, size, n_qry, n_slices, T);
+    plan_train(A, step_dims(batch, size, n_qry, n_slices), T);
     return A.off * sizeof(float);
 }
 
@@ -262,7 +282,6 @@ extern "C" size_t s3d_train_workspace_bytes(int batch, int size, long n_qry, int
 struct TrainRun {
     hipStream_t st;
     TrainBufs& T;
-    int B, S, ns, Nd;
     int prec;
     const BnSync* sync = nullptr;   // cross-rank BatchNorm statistics (S3dTrainBatch.sync_bn)
     bool conv_single = false;       // S3D_PREC_F16 step: the conv engine's forward / data-gradient passes run one f16 MFMA per product
@@ -325,6 +344,38 @@ struct TrainRun {
         a.prec = prec;
         return a;
     }
+    // the same for row matrices: dy (rows, n), x (rows, k)
+    WgradArgs wg_rows(const float* dy, int n, const float* x, int k, long rows) const {
+        return wg(dy, n, n, plain_src(x, k), k, 1, 1, (int)rows, 1);
+    }
+    // out (N,H,W, w's padded channels) = act(conv_ks(x (N,H,W,cx)) + shift), one plain NHWC source; accumulate: out +=
+    int conv(const FragW& w, int N, int H, int W, int ks, const float* x, int cx, float* out, const float* shift = nullptr,
+             int act = S3D_ACT_NONE, int accumulate = 0) const {
+        ConvLaunch c = mk(w, N, H, W, ks, shift, act);
+        c.nsrc = 1;
+        c.src[0] = plain_src(x, cx);
+        c.out = out;
+        c.out_accumulate = accumulate;
+        return launch_conv(c, st);
+    }
+    // weight gradient into a linear layer's [n][ld] layout (bias_out: its bias gradient, the column sums of dy) ...
+    int wgrad_lin(WgradArgs w, const void* out, int ld, const void* bias_out = nullptr, int single = 0) const {
+        w.out = (float*)out; w.out_kind = S3D_PACK_LINEAR; w.ld = ld;
+        w.bias_out = (float*)bias_out;
+        w.single = single;
+        return launch_wgrad(w, st);
+    }
+    // ... and into input channels [cin_begin, cin_begin + w.Cx) of a convolution's [n][cin_tot][taps] layout
+    int wgrad_conv(WgradArgs w, const void* out, int cin_tot, int cin_begin) const {
+        w.out = (float*)out; w.out_kind = S3D_PACK_CONV; w.cin_tot = cin_tot; w.cin_begin = cin_begin;
+        return launch_wgrad(w, st);
+    }
+    // weight gradient of a layer with 3 inputs (fc_p, pts_feat_extractor.0): x4 holds its input rows padded to 4, the [n][4]
+    // result goes through T.vec to the [n][3] parameter layout
+    int wgrad_xyz(const float* dy, int n, const float* x4, long rows, const void* out) const {
+        TRY_RET(wgrad_lin(wg_rows(dy, n, x4, 4, rows), T.vec, 4));
+        return launch_copy_cols(T.vec, (float*)out, n, 4, 3, st);
+    }
     int zero(float* p, size_t n) const {
         if (hipMemsetAsync(p, 0, n * sizeof(float), st) != hipSuccess) {
             s3d_set_error("train: memset failed");
@@ -367,11 +418,7 @@ static int enc_forward(const TrainRun& R, const S3dConvParams* enc, const float*
         if (i == 0 && S % 4 == 0) {   // 3 -> 64 straight from the image (T.in16 is still the wgrad's operand)
             TRY_RET(launch_conv3x3_first(img_nchw, 3, enc[0].w, enc[0].b, T.z[0], n_img, S, S, st));
         } else {
-            ConvLaunch c = R.mk(T.w_enc[i], n_img, r, r, 3, enc[i].b, S3D_ACT_NONE);
-            c.nsrc = 1;
-            c.src[0] = plain_src(T.ein[i], pad16(kEncCin[i]));
-            c.out = T.z[i];
-            TRY_RET(launch_conv(c, st));
+            TRY_RET(R.conv(T.w_enc[i], n_img, r, r, 3, T.ein[i], pad16(kEncCin[i]), T.z[i], enc[i].b));
         }
         if (i < 12 || (bn_last && enc[i].bn[2]))
             TRY_RET(launch_bn_stats(T.z[i], (long)n_img * r * r, kEncCout[i], T.mean[i], T.rstd[i],
@@ -399,10 +446,9 @@ static int enc_backward(const TrainRun& R, const S3dConvParams* enc, const S3dCo
         const long P = (long)n_img * r * r;
         // dcur = d z[i]
         TRY_RET(launch_colsum(dcur, P, kEncCout[i], 0, kEncCout[i], (float*)denc[i].b, 0, T.cpartial, st));
-        WgradArgs w = R.wg(dcur, kEncCout[i], kEncCout[i], plain_src(T.ein[i], pad16(kEncCin[i])),
-                           pad16(kEncCin[i]), n_img, r, r, 3);
-        w.out = (float*)denc[i].w; w.out_kind = S3D_PACK_CONV; w.cin_tot = kEncCin[i]; w.cin_begin = 0;
-        TRY_RET(launch_wgrad(w, st));
+        TRY_RET(R.wgrad_conv(R.wg(dcur, kEncCout[i], kEncCout[i], plain_src(T.ein[i], pad16(kEncCin[i])), pad16(kEncCin[i]),
+                                  n_img, r, r, 3),
+                             denc[i].w, kEncCin[i], 0));
         if (i == 7 && (ev_deep || inv_gs != 1.f)) {
             if (inv_gs != 1.f) {
                 ScaleTable tb;
@@ -413,11 +459,7 @@ static int enc_backward(const TrainRun& R, const S3dConvParams* enc, const S3dCo
             if (ev_deep) (void)hipEventRecord(ev_deep, st);
         }
         if (i == 0) break;
-        ConvLaunch c = R.mk(T.w_enc_d[i], n_img, r, r, 3, nullptr, S3D_ACT_NONE);
-        c.nsrc = 1;
-        c.src[0] = plain_src(dcur, kEncCout[i]);
-        c.out = dnext;   // d ein[i]  (grid of ein[i])
-        TRY_RET(launch_conv(c, st));
+        TRY_RET(R.conv(T.w_enc_d[i], n_img, r, r, 3, dcur, kEncCout[i], dnext));   // d ein[i]  (grid of ein[i])
         // ein[i] = [pool](relu(bn(z[i-1])))  ->  d z[i-1]
         const int j = i - 1, rj = S >> kEncRes[j];
         const float* skip = nullptr;
@@ -569,18 +611,11 @@ struct DecoderTrain {
         TRY_RET(launch_ln_bwd(l2_u1c(), P[2].norm1_w, dy, du, rows0, (float*)g.norm1_w, (float*)g.norm1_b, 0, T.cpartial,
                               st, &d1b, const_cast<float*>(dum), (float*)g.out_proj_b));
         // d Naug = dum^T [xbar | sigma],  d [xbar | sigma] = dum Naug
-        WgradArgs wn = R.wg(dum, 128, 128, plain_src(T.xbar, S3D_ABS_NA), S3D_ABS_NA, 1, 1, (int)rows0, 1);
-        wn.out = T.dNb; wn.out_kind = S3D_PACK_LINEAR; wn.ld = S3D_ABS_NA;
-        wn.single = single;
-        TRY_RET(launch_wgrad(wn, st));
+        TRY_RET(R.wgrad_lin(R.wg_rows(dum, 128, T.xbar, S3D_ABS_NA, rows0), T.dNb, S3D_ABS_NA, nullptr, single));
         TRY_RET(lin(T.w_absNT, S3D_ABS_NA, 128, nullptr, dum, rows0, T.dxbar, nullptr, 0));
         // the mix backward writes d xin of every token (value path + score path) and d qt
         TRY_RET(launch_attn_mix0_bwd(xin, T.qt, T.dxbar, dx_out, T.dqt, G, Tn, drop(2, 0), st));
-        WgradArgs wm = R.wg(T.dqt, 512, 512, plain_src(l2_x0c(), 128), 128, 1, 1, (int)rows0, 1);
-        wm.out = T.dMb; wm.out_kind = S3D_PACK_LINEAR; wm.ld = 128;
-        wm.bias_out = T.dmb;
-        wm.single = single;
-        TRY_RET(launch_wgrad(wm, st));
+        TRY_RET(R.wgrad_lin(R.wg_rows(T.dqt, 512, l2_x0c(), 128, rows0), T.dMb, 128, T.dmb, single));
         // chain rule through the absorbed products: in_proj weight / bias and out_proj weight (every element written)
         TRY_RET(launch_absorb_grad(P[2].in_proj_w, P[2].in_proj_b, P[2].out_proj_w, T.dMb, T.dmb, T.dNb, (float*)g.in_proj_w,
                                    (float*)g.in_proj_b, (float*)g.out_proj_w, st));
@@ -681,12 +716,12 @@ struct DecoderTrain {
             TRY_RET(lin(T.w_2T[l], 2048, 128, nullptr, dub, nb, T.ffD, nullptr, 0, nullptr, S3D_ACT_NONE, 0, T.ffA,
                     d2.scale));
             const int acc = r0 > 0;
-            WgradArgs w2 = R.wg(dub, 128, 128, plain_src(T.ffA, 2048), 2048, 1, 1, (int)nb, 1);
-            w2.out = (float*)g.lin2_w; w2.out_kind = S3D_PACK_LINEAR; w2.ld = 2048; w2.accumulate = acc;
-            TRY_RET(launch_wgrad(w2, st));
-            WgradArgs w1 = R.wg(T.ffD, 2048, 2048, plain_src(xb, 128), 128, 1, 1, (int)nb, 1);
-            w1.out = (float*)g.lin1_w; w1.out_kind = S3D_PACK_LINEAR; w1.ld = 128; w1.accumulate = acc;
-            TRY_RET(launch_wgrad(w1, st));
+            WgradArgs w2 = R.wg_rows(dub, 128, T.ffA, 2048, nb);
+            w2.accumulate = acc;
+            TRY_RET(R.wgrad_lin(w2, g.lin2_w, 2048));
+            WgradArgs w1 = R.wg_rows(T.ffD, 2048, xb, 128, nb);
+            w1.accumulate = acc;
+            TRY_RET(R.wgrad_lin(w1, g.lin1_w, 128));
             TRY_RET(launch_colsum(T.ffD, nb, 2048, 0, 2048, (float*)g.lin1_b, acc, T.cpartial, st));
             TRY_RET(lin(T.w_1T[l], 128, 2048, nullptr, T.ffD, nb, dx_out + r0 * 128, du + r0 * 128, 0));  // dx = da W1 + du
         }
@@ -700,21 +735,15 @@ struct DecoderTrain {
         const float* dum = dropout_p > 0.f ? T.dmask : du;
         TRY_RET(launch_ln_bwd(T.u1[l], P[l].norm1_w, dy, du, rows, (float*)g.norm1_w, (float*)g.norm1_b, 0, T.cpartial, st,
                               &d1b, const_cast<float*>(dum), (float*)g.out_proj_b));
-        WgradArgs wo = R.wg(dum, 128, 128, plain_src(T.O[l], 128), 128, 1, 1, (int)rows, 1);
-        wo.out = (float*)g.out_proj_w; wo.out_kind = S3D_PACK_LINEAR; wo.ld = 128;
-        wo.single = single;
-        TRY_RET(launch_wgrad(wo, st));
+        TRY_RET(R.wgrad_lin(R.wg_rows(dum, 128, T.O[l], 128, rows), g.out_proj_w, 128, nullptr, single));
         TRY_RET(lin(T.w_outT[l], 128, 128, nullptr, dum, rows, T.dO, nullptr, 0));             // dO = du Wo
         const LayerPtrs lpl = layer_ptrs(packed, HL, l);
         if (fused_attn(lpl))   // the forward kept no Q / K / V: the core backward recomputes them on chip (train_attnq.hip)
             TRY_RET(launch_attn_bwd_q(xi, T.dO, T.dQKV, G, Tn, lpl, drop(l, 0), st, single));
         else
             TRY_RET(launch_attn_core_bwd(T.QKV[l], T.dO, T.dQKV, G, Tn, drop(l, 0), st));
-        WgradArgs wi = R.wg(T.dQKV, 384, 384, plain_src(xi, 128), 128, 1, 1, (int)rows, 1);
-        wi.out = (float*)g.in_proj_w; wi.out_kind = S3D_PACK_LINEAR; wi.ld = 128;
-        wi.bias_out = (float*)g.in_proj_b;   // column sums of dQKV, added up while the kernel converts its rows
-        wi.single = single;
-        TRY_RET(launch_wgrad(wi, st));
+        // (in_proj's bias gradient = the column sums of dQKV, added up while the kernel converts its rows)
+        TRY_RET(R.wgrad_lin(R.wg_rows(T.dQKV, 384, xi, 128, rows), g.in_proj_w, 128, g.in_proj_b, single));
         TRY_RET(lin(T.w_inT[l], 128, 384, nullptr, T.dQKV, rows, dx_out, du, 0));              // dx = dQKV Win + du
         return 0;
     }
@@ -736,291 +765,300 @@ struct DecoderTrain {
     }
 };
 
-// The train step as three phases, so that a host can also drive it the way autograd does:
-//   PH_FWD   weight packs, U-Net / decoder / VGG19 forward with every activation kept in the workspace
-//   PH_LOSS  the reference's three losses and their gradients (train.py:29-47), created inside
-//   PH_BWD   decoder / VGG / U-Net backward into the parameter gradients
-// s3d_train_fwd_bwd runs all three; s3d_train_fwd = PH_FWD (returns sdf_pred, slices_rec, vgg_loss), s3d_train_bwd =
-// PH_BWD from caller-supplied output gradients (TrainExt) on the workspace the forward left behind.
-enum { PH_FWD = 1, PH_LOSS = 2, PH_BWD = 4 };
+// ------------------------------------------------------------------------------------------------
+// What every training entry point does before its first launch: argument checks, the derived sizes, the workspace plan
+// (X: the GT model's extra buffers, NULL for the Reg model) and the workspace-size check.  `who` prefixes the message.
+// ------------------------------------------------------------------------------------------------
+struct GtTrainBufs;
+static void plan_train_gt(Arena& A, const StepDims& d, TrainBufs& T, GtTrainBufs& X);   // api_train_gt.inc
+static int open_step(const char* who, bool pointers_ok, int B, int S, long Q, int ns, float dropout_p, int prec,
+                     bool prec_ok, void* workspace, size_t workspace_bytes, StepDims& d, TrainBufs& T, GtTrainBufs* X) {
+    S3D_CHECK_ARG(pointers_ok && workspace, "%s: null argument", who);
+    S3D_CHECK_ARG(B >= 1 && S >= 16 && S % 16 == 0 && Q >= 1 && ns >= 1 && ns <= 12, "%s: bad dims", who);
+    S3D_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "%s: dropout %g out of range", who, (double)dropout_p);
+    S3D_CHECK_ARG(prec_ok, "%s: precision mode %d", who, prec);
+    d = step_dims(B, S, Q, ns);
+    Arena A{(float*)workspace, 0};
+    if (X) plan_train_gt(A, d, T, *X);
+    else plan_train(A, d, T);
+    if (workspace_bytes < A.off * sizeof(float)) {
+        s3d_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, A.off * sizeof(float));
+        return S3D_E_WORKSPACE;
+    }
+    return 0;
+}
+
+// What the two training steps share once they are open: sizes and workspace, the conv / GEMM launcher, the locality order of
+// the queries, the transformer decoder, and the backward scale with its removal from the finished gradients.
+struct TrainStep {
+    const S3dTrainBatch* batch;
+    const StepDims d;
+    TrainBufs& T;
+    hipStream_t st;
+    // S3D_PREC_F16 (round 6): a THROUGHPUT mode of the step — the decoder's GEMMs (the four FFN kernels, the fused attention
+    // forward / backward, the row-linear layers and their weight gradients: ~75 % of the step's time) run ONE f16 MFMA per
+    // product instead of three; everything else (U-Net, VGG, sampling, all reductions, fp32 master weights, fp32 accumulation,
+    // the power-of-two backward scale) is the S3D_PREC_F16X3 path.  Not fp32-class: reported beside the headline, never instead.
+    const bool dec_single;
+    TrainRun R;
+    const int* perm;   // token rows follow the image-space locality order of the queries (sampler gathers / scatter-adds stay local)
+    DecoderTrain D;
+    float gs;          // every loss gradient carries gs (backward_scale); rescale() removes it from the parameter gradients
+
+    TrainStep(const S3dTrainBatch* batch_, const StepDims& d_, TrainBufs& T_, void* stream, int prec, float dropout_p,
+              unsigned long long seed, const S3dLayerParams* P, const S3dLayerParams* dP, const float* fc_out_w,
+              const float* d_fc_out_w, const float* d_fc_out_b, const HeadLayout& HL)
+        : batch(batch_), d(d_), T(T_), st((hipStream_t)stream), dec_single(prec == S3D_PREC_F16),
+          R{st, T, dec_single ? S3D_PREC_F16X3 : prec, batch_->sync_bn},
+          perm(d.Q >= S3D_SORT_MIN_QUERIES ? T.perm : nullptr),
+          D{R, T, st, P, dP, fc_out_w, (float*)d_fc_out_w, (float*)d_fc_out_b, T.head_packed, HL, R.prec, dropout_p, seed,
+            d.G, d.gpb, d.Q, d.rows, d.rows0, d.Tn, perm, dec_single},
+          gs(backward_scale(R.prec, d.nsdf)) {
+        if (dec_single) if (const char* e = getenv("S3D_TRAIN_F16_CONV")) R.conv_single = atoi(e) != 0;
+    }
+    int sort_queries() const {
+        return perm ? launch_query_sort(batch->qry, batch->rot, batch->trans, 0, d.B, d.Q, T.perm, T.sortws, st) : 0;
+    }
+    // the sampler backward's arguments that do not depend on the model
+    SampleBwdArgs sample_bwd_args(const float* dX) const {
+        SampleBwdArgs sb = {};
+        sb.dX = dX;
+        sb.qry = batch->qry; sb.rot = batch->rot; sb.trans = batch->trans;
+        sb.flip_yz = 0; sb.size = d.S; sb.n_slices = d.ns;
+        sb.n_qry = d.Q; sb.groups_per_batch = d.gpb; sb.groups = d.G;
+        sb.perm = perm; sb.bin_ends = perm ? T.sortws : nullptr;
+        sb.gxy = perm ? T.gxy : nullptr;
+        return sb;
+    }
+    int rescale(const ScaleTable& tb) const { return launch_scale_table(tb, 1.f / gs, st); }
+};
+
+// caller-supplied output gradients of s3d_train_bwd
 struct TrainExt {
     const float* d_sdf;   // d loss / d sdf_pred (B,Q), or NULL (zero)
     const float* d_rec;   // d loss / d slices_rec (B*ns,3,S,S), or NULL
     float d_vgg;          // d loss / d vgg_loss
     float grad_scale;     // power-of-two backward scale of the split-precision path; 0 = automatic (2^k ~ 8 * B*Q)
 };
-static int train_step_impl(const S3dUNetParams* U, const S3dHeadParams* Hd, const S3dVggParams* V,
-                           const S3dUNetParams* dU, const S3dHeadParams* dH, const S3dTrainBatch* batch,
-                           int B, int S, long Q, int ns, float dropout_p, unsigned long long seed, int prec,
-                           float* losses_out, float* sdf_pred_out, float* slices_rec_out, void* workspace,
-                           size_t workspace_bytes, void* stream, int phases, const TrainExt* ext) {
-    hipStream_t st = (hipStream_t)stream;
-    static const S3dUNetParams kNoU = {};
-    static const S3dHeadParams kNoH = {};
-    const bool fwd = phases & PH_FWD, loss = phases & PH_LOSS, bwd = phases & PH_BWD;
-    if (!bwd) {   // forward only: nothing is written through the gradient structs
-        if (!dU) dU = &kNoU;
-        if (!dH) dH = &kNoH;
-    }
-    S3D_CHECK_ARG(U && Hd && V && dU && dH && batch && losses_out && workspace, "train: null argument");
-    S3D_CHECK_ARG(B >= 1 && S >= 16 && S % 16 == 0 && Q >= 1 && ns >= 1 && ns <= 12, "train: bad dims");
-    S3D_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "train: dropout %g out of range", (double)dropout_p);
-    S3D_CHECK_ARG(loss || !bwd || ext, "train: backward without loss gradients");
-    Arena A{(float*)workspace, 0};
-    TrainBufs T;
-    plan_train(A, B, S, Q, ns, T);
-    if (workspace_bytes < A.off * sizeof(float)) {
-        s3d_set_error("train: workspace %zu < %zu bytes", workspace_bytes, A.off * sizeof(float));
-        return S3D_E_WORKSPACE;
-    }
-    const int Nd = B * ns;
-    S3D_CHECK_ARG(prec == S3D_PREC_F32 || prec == S3D_PREC_F16X3 || prec == S3D_PREC_F16, "train: precision mode %d", prec);
-    // S3D_PREC_F16 (round 6): a THROUGHPUT mode of the step — the decoder's GEMMs (the four FFN kernels, the fused attention
-    // forward / backward, the row-linear layers and their weight gradients: ~75 % of the step's time) run ONE f16 MFMA per
-    // product instead of three; everything else (U-Net, VGG, sampling, all reductions, fp32 master weights, fp32 accumulation,
-    // the power-of-two backward scale) is the S3D_PREC_F16X3 path.  Not fp32-class: reported beside the headline, never instead.
-    const bool dec_single = prec == S3D_PREC_F16;
-    if (dec_single) prec = S3D_PREC_F16X3;
-    TrainRun R{st, T, B, S, ns, Nd, prec, batch->sync_bn};
-    if (dec_single) if (const char* e = getenv("S3D_TRAIN_F16_CONV")) R.conv_single = atoi(e) != 0;
-    const int lc[5] = {512, 256, 128, 64, 32};
-    if (fwd) TRY(R.zero(losses_out, 4));
-    const HeadLayout HL = head_layout();
-    const int lo[3] = {0, 512, 768};
-    const int r5 = S / 16;
-    float* rec = slices_rec_out ? slices_rec_out : T.rec;
-    const long gpb = (Q + S3D_GROUP - 1) / S3D_GROUP, G = gpb * B;
-    const int Tn = ns + 1;
-    const long rows = G * Tn * S3D_GROUP, rows0 = G * S3D_GROUP;
-    // token rows follow the image-space locality order of the queries (sampler gathers / scatter-adds stay local)
-    const int* perm = Q >= S3D_SORT_MIN_QUERIES ? T.perm : nullptr;
-    DecoderTrain D{R, T, st, Hd->layer, dH->layer, Hd->fc_out_w, (float*)dH->fc_out_w, (float*)dH->fc_out_b,
-                   T.head_packed, HL, prec, dropout_p, seed, G, gpb, Q, rows, rows0, Tn, perm, dec_single};
-    float* sdf = sdf_pred_out ? sdf_pred_out : T.sdf;
-    const long nsdf = (long)B * Q, nimg = (long)Nd * 3 * S * S;
-    // every loss gradient carries gs; it is removed from the parameter gradients at the end
-    const float gs = (ext && ext->grad_scale > 0.f && prec == S3D_PREC_F16X3) ? ext->grad_scale : backward_scale(prec, nsdf);
-    const int N2 = 2 * Nd;
-    hipEvent_t ev[3] = {(hipEvent_t)batch->ev_grad_ready[0], (hipEvent_t)batch->ev_grad_ready[1],
-                        (hipEvent_t)batch->ev_grad_ready[2]};
 
-    RangeSeq range;   // roctx: one range per phase of the step
-    if (fwd) {
-    // =========================================================================================
-    // 1. weight packs (forward + data-gradient forms)
-    // =========================================================================================
-    range.next("s3d:train:weight_packs");
-    PackBatchScope packs;   // the ~270 weight repacks of a step go out as table launches at packs.flush()
-    TRY(enc_pack(R, U->enc));
-    TRY(R.pack_lin(T.w_transc, U->trans_c.w, 512, 640, 640));
-    TRY(R.pack_dgrad(T.w_transc_d, U->trans_c.w, 512, 640, 0, 512, 1));
-    for (int i = 0; i < 4; ++i) {
-        const int C = kUpC[i], Ct = C / 2;
-        TRY(R.pack_lin(T.w_tup[i], U->trans_up[i].w, Ct, C, C));
-        TRY(R.pack_dgrad(T.w_tup_d[i], U->trans_up[i].w, Ct, C, 0, C, 1));
-        PackArgs a = {};
-        a.src = U->up_t[i].w; a.dst = T.w_upt[i].p; a.kind = S3D_PACK_CONVT;
-        a.n_valid = 4 * Ct; a.n_pad = 4 * Ct; a.KU_total = C / 16; a.ku_seg = C / 16; a.k_valid = C; a.ct = Ct;
-        TRY(launch_pack(a, st));
-        if (prec == S3D_PREC_F16X3) {
-            a.f16 = 1; a.dst = T.w_upt[i].p16;
-            TRY(launch_pack(a, st));
-        }
-        PackArgs d = {};
-        d.src = U->up_t[i].w; d.dst = T.w_upt_d[i].p; d.kind = S3D_PACK_CONVT_DGRAD;
-        d.n_valid = C; d.n_pad = C; d.KU_total = 4 * Ct / 16; d.ku_seg = 4 * Ct / 16; d.ct = Ct;
-        TRY(launch_pack(d, st));
-        if (prec == S3D_PREC_F16X3) {
-            d.f16 = 1; d.dst = T.w_upt_d[i].p16;
-            TRY(launch_pack(d, st));
-        }
-        TRY(launch_fold_bn(U->up_t[i].b, nullptr, T.vec, T.upt_shift[i], Ct, 4 * Ct, 4, 0, st));
-        TRY(R.pack_conv(T.w_c1[i], U->up_c1[i].w, Ct, C, 0, Ct, 0, 9));
-        TRY(R.pack_conv(T.w_c1[i], U->up_c1[i].w, Ct, C, Ct, Ct, 9 * Ct / 16, 9));
-        TRY(R.pack_dgrad(T.w_c1_dp[i], U->up_c1[i].w, Ct, C, 0, Ct, 9));
-        TRY(R.pack_dgrad(T.w_c1_du[i], U->up_c1[i].w, Ct, C, Ct, Ct, 9));
-        TRY(R.pack_conv(T.w_c2[i], U->up_c2[i].w, Ct, Ct, 0, Ct, 0, 9));
-        TRY(R.pack_dgrad(T.w_c2_d[i], U->up_c2[i].w, Ct, Ct, 0, Ct, 9));
-    }
-    TRY(R.pack_lin(T.w_outc, U->outc.w, 3, 32, 32));
-    TRY(R.pack_dgrad(T.w_outc_d, U->outc.w, 3, 32, 0, 32, 1));
-    TRY(launch_fold_bn(U->outc.b, nullptr, T.vec, T.outc_shift, 3, 16, 1, 0, st));
-    for (int i = 0; i < 14; ++i) {
-        TRY(R.pack_conv(T.w_vgg[i], V->conv[i].w, kVggCout[i], kVggCin[i], 0, kVggCin[i], 0, 9));
-        TRY(R.pack_dgrad(T.w_vgg_d[i], V->conv[i].w, kVggCout[i], kVggCin[i], 0, kVggCin[i], 9));
-    }
-    TRY(R.pack_lin_t(T.w_vggZ, V->conv[0].w, 27, 64, 27));   // elem(n = ci*9 + tap, k = co) = w[co*27 + n]
-    TRY(head_pack_impl(Hd, T.head_packed, head_layout().total * sizeof(float), stream, false));   // no bf16 twins: the trainer never decodes in bf16
-    for (int l = 0; l < 3; ++l) TRY(R.pack_lin_t(T.w_projT[l], Hd->fc_s_w + lo[l], lc[l], 128, 992));
-    {
-        FragW f{T.ws34_t, T.ws34_t16, 96, 8};
-        TRY(R.pack_lin_t(f, Hd->fc_s_w + 896, 96, 128, 992));
-    }
-    {
-        DecoderTrain Dp{R, T, st, Hd->layer, dH->layer, nullptr, nullptr, nullptr, nullptr, HL, prec, dropout_p, seed,
-                        0, 0, 0, 0, 0, 0, nullptr};
-        TRY(Dp.pack_layers());
-    }
-    TRY(packs.flush(st));
+// The Reg model's step, one method per phase (the roctx ranges carry the same names), so that a host can also drive it the way
+// autograd does: s3d_train_fwd_bwd = weight packs, the forwards, the reference's losses, the backwards; s3d_train_fwd = packs,
+// forwards and the value of vgg_loss, every activation kept in the workspace; s3d_train_bwd = the backwards from caller-supplied
+// output gradients (TrainExt) on the workspace the forward left behind.
+struct RegStep : TrainStep {
+    const S3dUNetParams *U, *dU;   // dU, dH: NULL in a forward-only step
+    const S3dHeadParams *Hd, *dH;
+    const S3dVggParams* V;
+    float *sdf, *rec;              // the step's outputs: the caller's buffers, or the workspace's
+    RangeSeq range;                // roctx: one range per phase of the step
 
-    // =========================================================================================
-    // 2. U-Net forward, train-mode BatchNorm (unet_custom.py:40-69)
-    // =========================================================================================
-    range.next("s3d:train:unet_fwd");
-    TRY(enc_forward(R, U->enc, batch->img, B, S, 0));
-    {
-        ConvLaunch c = R.mk(T.w_transc, Nd, r5, r5, 1, U->trans_c.b, S3D_ACT_NONE);
-        c.nsrc = 2;
-        c.src[0] = ConvSrc{T.z[12], 512, ns, 0, 0};
-        c.src[1] = ConvSrc{U->emds, 128, 1, ns, 1};
-        c.out = T.F[0];
-        TRY(launch_conv(c, st));
+    RegStep(const S3dUNetParams* U_, const S3dHeadParams* Hd_, const S3dVggParams* V_, const S3dUNetParams* dU_,
+            const S3dHeadParams* dH_, const S3dTrainBatch* batch_, const StepDims& d_, TrainBufs& T_, float dropout_p,
+            unsigned long long seed, int prec, float* sdf_pred_out, float* slices_rec_out, void* stream)
+        : TrainStep(batch_, d_, T_, stream, prec, dropout_p, seed, Hd_->layer, dH_ ? dH_->layer : nullptr, Hd_->fc_out_w,
+                    dH_ ? dH_->fc_out_w : nullptr, dH_ ? dH_->fc_out_b : nullptr, head_layout()),
+          U(U_), dU(dU_), Hd(Hd_), dH(dH_), V(V_), sdf(sdf_pred_out ? sdf_pred_out : T_.sdf),
+          rec(slices_rec_out ? slices_rec_out : T_.rec) {}
+
+    // ---- 1. weight packs (forward + data-gradient forms) ----
+    int pack_weights() {
+        range.next("s3d:train:weight_packs");
+        const int prec = R.prec;
+        PackBatchScope packs;   // the ~270 weight repacks of a step go out as table launches at packs.flush()
+        TRY_RET(enc_pack(R, U->enc));
+        TRY_RET(R.pack_lin(T.w_transc, U->trans_c.w, 512, 640, 640));
+        TRY_RET(R.pack_dgrad(T.w_transc_d, U->trans_c.w, 512, 640, 0, 512, 1));
+        for (int i = 0; i < 4; ++i) {
+            const int C = kUpC[i], Ct = C / 2;
+            TRY_RET(R.pack_lin(T.w_tup[i], U->trans_up[i].w, Ct, C, C));
+            TRY_RET(R.pack_dgrad(T.w_tup_d[i], U->trans_up[i].w, Ct, C, 0, C, 1));
+            PackArgs a = {};
+            a.src = U->up_t[i].w; a.dst = T.w_upt[i].p; a.kind = S3D_PACK_CONVT;
+            a.n_valid = 4 * Ct; a.n_pad = 4 * Ct; a.KU_total = C / 16; a.ku_seg = C / 16; a.k_valid = C; a.ct = Ct;
+            TRY_RET(launch_pack(a, st));
+            if (prec == S3D_PREC_F16X3) {
+                a.f16 = 1; a.dst = T.w_upt[i].p16;
+                TRY_RET(launch_pack(a, st));
+            }
+            PackArgs g = {};
+            g.src = U->up_t[i].w; g.dst = T.w_upt_d[i].p; g.kind = S3D_PACK_CONVT_DGRAD;
+            g.n_valid = C; g.n_pad = C; g.KU_total = 4 * Ct / 16; g.ku_seg = 4 * Ct / 16; g.ct = Ct;
+            TRY_RET(launch_pack(g, st));
+            if (prec == S3D_PREC_F16X3) {
+                g.f16 = 1; g.dst = T.w_upt_d[i].p16;
+                TRY_RET(launch_pack(g, st));
+            }
+            TRY_RET(launch_fold_bn(U->up_t[i].b, nullptr, T.vec, T.upt_shift[i], Ct, 4 * Ct, 4, 0, st));
+            TRY_RET(R.pack_conv(T.w_c1[i], U->up_c1[i].w, Ct, C, 0, Ct, 0, 9));
+            TRY_RET(R.pack_conv(T.w_c1[i], U->up_c1[i].w, Ct, C, Ct, Ct, 9 * Ct / 16, 9));
+            TRY_RET(R.pack_dgrad(T.w_c1_dp[i], U->up_c1[i].w, Ct, C, 0, Ct, 9));
+            TRY_RET(R.pack_dgrad(T.w_c1_du[i], U->up_c1[i].w, Ct, C, Ct, Ct, 9));
+            TRY_RET(R.pack_conv(T.w_c2[i], U->up_c2[i].w, Ct, Ct, 0, Ct, 0, 9));
+            TRY_RET(R.pack_dgrad(T.w_c2_d[i], U->up_c2[i].w, Ct, Ct, 0, Ct, 9));
+        }
+        TRY_RET(R.pack_lin(T.w_outc, U->outc.w, 3, 32, 32));
+        TRY_RET(R.pack_dgrad(T.w_outc_d, U->outc.w, 3, 32, 0, 32, 1));
+        TRY_RET(launch_fold_bn(U->outc.b, nullptr, T.vec, T.outc_shift, 3, 16, 1, 0, st));
+        for (int i = 0; i < 14; ++i) {
+            TRY_RET(R.pack_conv(T.w_vgg[i], V->conv[i].w, kVggCout[i], kVggCin[i], 0, kVggCin[i], 0, 9));
+            TRY_RET(R.pack_dgrad(T.w_vgg_d[i], V->conv[i].w, kVggCout[i], kVggCin[i], 0, kVggCin[i], 9));
+        }
+        TRY_RET(R.pack_lin_t(T.w_vggZ, V->conv[0].w, 27, 64, 27));   // elem(n = ci*9 + tap, k = co) = w[co*27 + n]
+        // (no bf16 twins: the trainer never decodes in bf16)
+        TRY_RET(head_pack_impl(Hd, T.head_packed, D.HL.total * sizeof(float), st, false));
+        for (int l = 0; l < 3; ++l) TRY_RET(R.pack_lin_t(T.w_projT[l], Hd->fc_s_w + kFcsCol[l], kLatC[l], 128, 992));
+        {
+            FragW f{T.ws34_t, T.ws34_t16, 96, 8};
+            TRY_RET(R.pack_lin_t(f, Hd->fc_s_w + 896, 96, 128, 992));
+        }
+        TRY_RET(D.pack_layers());
+        return packs.flush(st);
     }
-    for (int i = 0; i < 4; ++i) {
-        const int C = kUpC[i], Ct = C / 2, rp = r5 << i, ro = rp * 2;
-        const long Pd = (long)Nd * ro * ro;
+
+    // ---- 2. U-Net forward, train-mode BatchNorm (unet_custom.py:40-69) ----
+    int unet_forward() {
+        range.next("s3d:train:unet_fwd");
+        const int B = d.B, S = d.S, ns = d.ns, Nd = d.Nd, r5 = d.r5;
+        TRY_RET(enc_forward(R, U->enc, batch->img, B, S, 0));
         {
-            ConvLaunch c = R.mk(T.w_tup[i], B, ro, ro, 1, U->trans_up[i].b, S3D_ACT_NONE);
-            c.nsrc = 1;
-            c.src[0] = plain_src(T.z[kTapConv[3 - i]], C);
-            c.out = T.proj[i];
-            TRY(launch_conv(c, st));
-        }
-        {
-            ConvLaunch c = R.mk(T.w_upt[i], Nd, rp, rp, 1, T.upt_shift[i], S3D_ACT_NONE);
-            c.nsrc = 1;
-            c.src[0] = plain_src(T.F[i], C);
-            c.out = T.up[i];
-            c.out_mode = S3D_OUT_CONVT;
-            c.cout_store = Ct;
-            TRY(launch_conv(c, st));
-        }
-        {
-            ConvLaunch c = R.mk(T.w_c1[i], Nd, ro, ro, 3, nullptr, S3D_ACT_NONE);
+            ConvLaunch c = R.mk(T.w_transc, Nd, r5, r5, 1, U->trans_c.b, S3D_ACT_NONE);
             c.nsrc = 2;
-            c.src[0] = ConvSrc{T.proj[i], Ct, ns, 0, 0};
-            c.src[1] = plain_src(T.up[i], Ct);
-            c.out = T.z1[i];
-            TRY(launch_conv(c, st));
+            c.src[0] = ConvSrc{T.z[12], 512, ns, 0, 0};
+            c.src[1] = ConvSrc{U->emds, 128, 1, ns, 1};
+            c.out = T.F[0];
+            TRY_RET(launch_conv(c, st));
         }
-        TRY(launch_bn_stats(T.z1[i], Pd, Ct, T.m1[i], T.r1[i], (float*)U->up_c1[i].bn[2], (float*)U->up_c1[i].bn[3],
-                            T.cpartial, st, R.sync));
-        TRY(launch_bn_apply(T.z1[i], T.m1[i], T.r1[i], U->up_c1[i].bn[0], U->up_c1[i].bn[1], T.mid[i], Nd, ro, ro, Ct,
-                            0, st));
-        {
-            ConvLaunch c = R.mk(T.w_c2[i], Nd, ro, ro, 3, nullptr, S3D_ACT_NONE);
-            c.nsrc = 1;
-            c.src[0] = plain_src(T.mid[i], Ct);
-            c.out = T.z2[i];
-            TRY(launch_conv(c, st));
+        for (int i = 0; i < 4; ++i) {
+            const int C = kUpC[i], Ct = C / 2, rp = r5 << i, ro = rp * 2;
+            const long Pd = (long)Nd * ro * ro;
+            TRY_RET(R.conv(T.w_tup[i], B, ro, ro, 1, T.z[kTapConv[3 - i]], C, T.proj[i], U->trans_up[i].b));
+            {
+                ConvLaunch c = R.mk(T.w_upt[i], Nd, rp, rp, 1, T.upt_shift[i], S3D_ACT_NONE);
+                c.nsrc = 1;
+                c.src[0] = plain_src(T.F[i], C);
+                c.out = T.up[i];
+                c.out_mode = S3D_OUT_CONVT;
+                c.cout_store = Ct;
+                TRY_RET(launch_conv(c, st));
+            }
+            {
+                ConvLaunch c = R.mk(T.w_c1[i], Nd, ro, ro, 3, nullptr, S3D_ACT_NONE);
+                c.nsrc = 2;
+                c.src[0] = ConvSrc{T.proj[i], Ct, ns, 0, 0};
+                c.src[1] = plain_src(T.up[i], Ct);
+                c.out = T.z1[i];
+                TRY_RET(launch_conv(c, st));
+            }
+            TRY_RET(launch_bn_stats(T.z1[i], Pd, Ct, T.m1[i], T.r1[i], (float*)U->up_c1[i].bn[2], (float*)U->up_c1[i].bn[3],
+                                    T.cpartial, st, R.sync));
+            TRY_RET(launch_bn_apply(T.z1[i], T.m1[i], T.r1[i], U->up_c1[i].bn[0], U->up_c1[i].bn[1], T.mid[i], Nd, ro, ro, Ct,
+                                    0, st));
+            TRY_RET(R.conv(T.w_c2[i], Nd, ro, ro, 3, T.mid[i], Ct, T.z2[i]));
+            TRY_RET(launch_bn_stats(T.z2[i], Pd, Ct, T.m2[i], T.r2[i], (float*)U->up_c2[i].bn[2], (float*)U->up_c2[i].bn[3],
+                                    T.cpartial, st, R.sync));
+            TRY_RET(launch_bn_apply(T.z2[i], T.m2[i], T.r2[i], U->up_c2[i].bn[0], U->up_c2[i].bn[1], T.F[i + 1], Nd, ro, ro,
+                                    Ct, 0, st));
         }
-        TRY(launch_bn_stats(T.z2[i], Pd, Ct, T.m2[i], T.r2[i], (float*)U->up_c2[i].bn[2], (float*)U->up_c2[i].bn[3],
-                            T.cpartial, st, R.sync));
-        TRY(launch_bn_apply(T.z2[i], T.m2[i], T.r2[i], U->up_c2[i].bn[0], U->up_c2[i].bn[1], T.F[i + 1], Nd, ro, ro,
-                            Ct, 0, st));
-    }
-    {
         ConvLaunch c = R.mk(T.w_outc, Nd, S, S, 1, T.outc_shift, S3D_ACT_TANH);
         c.nsrc = 1;
         c.src[0] = plain_src(T.F[4], 32);
         c.out = rec;
         c.out_mode = S3D_OUT_NCHW;
         c.cout_store = 3;
-        TRY(launch_conv(c, st));
+        return launch_conv(c, st);
     }
 
-    // =========================================================================================
-    // 3. decoder forward (models.py:53-84), activations kept
-    // =========================================================================================
-    range.next("s3d:train:sample_and_decoder_fwd");
-    for (int l = 0; l < 3; ++l) {   // fp32 in every mode
-        const int r = r5 << l;
-        TRY(launch_conv(proj_desc(T.head_packed + HL.wproj[l], nullptr, false, 128, lc[l], T.F[l], Nd, r, r, T.lat_proj[l]),
-                        st));
-    }
-    {
+    // ---- 3. decoder forward (models.py:53-84), activations kept ----
+    int tokens_and_decoder_forward() {
+        range.next("s3d:train:sample_and_decoder_fwd");
+        const HeadLayout& HL = D.HL;
+        for (int l = 0; l < 3; ++l) {   // fp32 in every mode
+            const int r = d.r5 << l;
+            TRY_RET(launch_conv(proj_desc(T.head_packed + HL.wproj[l], nullptr, false, 128, kLatC[l], T.F[l], d.Nd, r, r,
+                                          T.lat_proj[l]),
+                                st));
+        }
         SampleArgs sa = {};
         for (int l = 0; l < 3; ++l) sa.proj[l] = T.lat_proj[l];
         sa.fine[0] = T.F[3]; sa.fine[1] = T.F[4];
-        sa.size = S; sa.n_slices = ns;
+        sa.size = d.S; sa.n_slices = d.ns;
         sa.fcp_w = T.head_packed + HL.fcp_w; sa.fcp_b = T.head_packed + HL.fcp_b;
         sa.fcs_b = T.head_packed + HL.fcs_b; sa.ws34 = T.head_packed + HL.ws34;
-        sa.ws34_16 = prec == S3D_PREC_F16X3 ? T.head_packed + HL.ws34_16 : nullptr;
+        sa.ws34_16 = R.prec == S3D_PREC_F16X3 ? T.head_packed + HL.ws34_16 : nullptr;
         sa.qry = batch->qry; sa.rot = batch->rot; sa.trans = batch->trans; sa.flip_yz = 0;
-        sa.n_qry = Q; sa.groups_per_batch = gpb; sa.g_begin = 0; sa.g_count = G;
+        sa.n_qry = d.Q; sa.groups_per_batch = d.gpb; sa.g_begin = 0; sa.g_count = d.G;
         sa.nx = 0; sa.box = 1.f; sa.X = T.X0; sa.raw_out = T.raw34;
-        if (perm) TRY(launch_query_sort(batch->qry, batch->rot, batch->trans, 0, B, Q, T.perm, T.sortws, st));
+        TRY_RET(sort_queries());
         sa.perm = perm;
         sa.lane_footprints = !s3d_shared_footprint();
-        TRY(launch_sample_tokens(sa, st));
-        TRY(launch_qry_rot_rows(batch->qry, batch->rot, 0, Q, gpb, G, perm, T.qrot4, st));
+        TRY_RET(launch_sample_tokens(sa, st));
+        TRY_RET(launch_qry_rot_rows(batch->qry, batch->rot, 0, d.Q, d.gpb, d.G, perm, T.qrot4, st));
+        return D.forward(T.X0, sdf);
     }
-    TRY(D.forward(T.X0, sdf));
 
     // ---- VGG19 forward on [pred ; target] (vgg_perceptual_loss.py:42-70), activations kept ----
-    range.next("s3d:train:vgg_fwd");
-    // conv1_1: in split precision its own kernel straight from the image pairs (K = 27 is one MFMA k-step; conv.hip); the
-    // fp32 mode normalises into a 16-channel NHWC image for the generic tile
-    const bool vgg_first_fused = prec == S3D_PREC_F16X3;
-    if (vgg_first_fused)
-        TRY(launch_vgg_first_f16x3(rec, batch->img_slices, V->mean, V->std, (const float*)V->conv[0].w,
-                                   (const float*)V->conv[0].b, T.va[0], Nd, S, st));
-    else
-        TRY(launch_vgg_prep(rec, batch->img_slices, V->mean, V->std, T.vin16, Nd, S, st));
-    {
+    int vgg_forward() {
+        range.next("s3d:train:vgg_fwd");
+        const int S = d.S, Nd = d.Nd, N2 = 2 * Nd;
+        // conv1_1: in split precision its own kernel straight from the image pairs (K = 27 is one MFMA k-step; conv.hip); the
+        // fp32 mode normalises into a 16-channel NHWC image for the generic tile
+        const bool vgg_first_fused = R.prec == S3D_PREC_F16X3;
+        if (vgg_first_fused)
+            TRY_RET(launch_vgg_first_f16x3(rec, batch->img_slices, V->mean, V->std, (const float*)V->conv[0].w,
+                                           (const float*)V->conv[0].b, T.va[0], Nd, S, st));
+        else
+            TRY_RET(launch_vgg_prep(rec, batch->img_slices, V->mean, V->std, T.vin16, Nd, S, st));
         const float* cur = vgg_first_fused ? T.va[0] : T.vin16;
         int curC = vgg_first_fused ? kVggCout[0] : 16, pi = 0;
         for (int i = vgg_first_fused ? 1 : 0; i < 14; ++i) {
             const int r = S >> kVggRes[i];
-            ConvLaunch c = R.mk(T.w_vgg[i], N2, r, r, 3, V->conv[i].b, i == 13 ? S3D_ACT_NONE : S3D_ACT_RELU);
-            c.nsrc = 1;
-            c.src[0] = plain_src(cur, curC);
-            c.out = T.va[i];
-            TRY(launch_conv(c, st));
+            TRY_RET(R.conv(T.w_vgg[i], N2, r, r, 3, cur, curC, T.va[i], V->conv[i].b, i == 13 ? S3D_ACT_NONE : S3D_ACT_RELU));
             cur = T.va[i];
             curC = kVggCout[i];
             if (kVggPoolAfter[i]) {
-                TRY(launch_bn_relu_pool(cur, nullptr, nullptr, T.vp[pi], N2, r, r, curC, st));
+                TRY_RET(launch_bn_relu_pool(cur, nullptr, nullptr, T.vp[pi], N2, r, r, curC, st));
                 cur = T.vp[pi++];
             }
         }
+        return 0;
     }
-    if (!loss) {   // forward-only call: the value of vgg_loss (models.py:92), no gradients
+    // forward-only step: the value of vgg_loss (models.py:92) added to *acc, no gradients
+    int vgg_loss_value(float* acc) {
         for (int i = 13; i >= 0; --i)
             if (kVggTap[i]) {
-                const long half = (long)Nd * (S >> kVggRes[i]) * (S >> kVggRes[i]) * kVggCout[i];
-                TRY(launch_l1_fwd_bwd(T.va[i], T.va[i] + half, half, 0.001f * kVggW[kVggTap[i] - 1] / (float)half,
-                                      nullptr, 0, T.cpartial, losses_out + 2, st));
+                const long half = (long)d.Nd * (d.S >> kVggRes[i]) * (d.S >> kVggRes[i]) * kVggCout[i];
+                TRY_RET(launch_l1_fwd_bwd(T.va[i], T.va[i] + half, half, 0.001f * kVggW[kVggTap[i] - 1] / (float)half, nullptr,
+                                          0, T.cpartial, acc, st));
             }
+        return 0;
     }
-    }   // fwd
 
-    // =========================================================================================
-    // 4. loss gradients: the reference's losses (train.py:29-39,46-47: L1(sdf) + L1(images) + 0.001 * VGG19
-    //    perceptual) created here, or the caller's output gradients (autograd-style backward)
-    // =========================================================================================
-    float* loss_vgg_acc = losses_out + 2;
-    float vgg_mul = 1.f;
-    range.next("s3d:train:losses_and_vgg_bwd");
-    if (loss) {
-        TRY(launch_l1_fwd_bwd(sdf, batch->sdf, nsdf, 1.f / (float)nsdf, T.dsdf, 0, T.cpartial, losses_out + 0, st, gs));
-        TRY(launch_l1_fwd_bwd(rec, batch->img_slices, nimg, 1.f / (float)nimg, T.drec, 0, T.cpartial, losses_out + 1, st,
-                              gs));
-        TRY(launch_scalar_reduce(sdf, batch->sdf, nsdf, 1, 1.f / (float)nsdf, losses_out + 3, 0, T.cpartial, st));
-    } else if (bwd) {
-        TRY(R.zero(T.dsdf, (size_t)nsdf));
-        if (ext->d_sdf) TRY(launch_axpy(T.dsdf, ext->d_sdf, gs, nsdf, st));
-        TRY(R.zero(T.drec, (size_t)nimg));
-        if (ext->d_rec) TRY(launch_axpy(T.drec, ext->d_rec, gs, nimg, st));
-        loss_vgg_acc = T.vec;     // the tap kernels also sum the loss: into scratch here
-        vgg_mul = ext->d_vgg;
+    // ---- 4. loss gradients: the reference's losses (train.py:29-39,46-47: L1(sdf) + L1(images) + 0.001 * VGG19 perceptual,
+    //      the last inside vgg_backward) into losses_out[0..3] with their gradients, or the caller's output gradients ----
+    int reference_loss_grads(float* losses_out) {
+        range.next("s3d:train:losses_and_vgg_bwd");
+        const long nsdf = d.nsdf, nimg = d.nimg;
+        TRY_RET(launch_l1_fwd_bwd(sdf, batch->sdf, nsdf, 1.f / (float)nsdf, T.dsdf, 0, T.cpartial, losses_out + 0, st, gs));
+        TRY_RET(launch_l1_fwd_bwd(rec, batch->img_slices, nimg, 1.f / (float)nimg, T.drec, 0, T.cpartial, losses_out + 1, st,
+                                  gs));
+        return launch_scalar_reduce(sdf, batch->sdf, nsdf, 1, 1.f / (float)nsdf, losses_out + 3, 0, T.cpartial, st);
     }
-    if (!bwd) return 0;
-    // ---- VGG backward (predicted branch = first Nd images), taps add their L1 gradients ----
-    if (loss || vgg_mul != 0.f) {
+    int external_loss_grads(const TrainExt& ext) {
+        range.next("s3d:train:losses_and_vgg_bwd");
+        if (ext.grad_scale > 0.f && R.prec == S3D_PREC_F16X3) gs = ext.grad_scale;
+        TRY_RET(R.zero(T.dsdf, (size_t)d.nsdf));
+        if (ext.d_sdf) TRY_RET(launch_axpy(T.dsdf, ext.d_sdf, gs, d.nsdf, st));
+        TRY_RET(R.zero(T.drec, (size_t)d.nimg));
+        if (ext.d_rec) TRY_RET(launch_axpy(T.drec, ext.d_rec, gs, d.nimg, st));
+        return 0;
+    }
+
+    // ---- VGG backward (predicted branch = first Nd images): the taps add vgg_mul times their L1 gradients, and their loss
+    //      terms to *loss_acc ----
+    int vgg_backward(float* loss_acc, float vgg_mul) {
+        const int S = d.S, Nd = d.Nd;
         float* dcur = T.vgA;
         float* dnext = T.vgB;
-        int pi = 3;
         for (int i = 13; i >= 0; --i) {
             const int r = S >> kVggRes[i];
             const long half = (long)Nd * r * r * kVggCout[i];
@@ -1030,16 +1068,12 @@ static int train_step_impl(const S3dUNetParams* U, const S3dHeadParams* Hd, cons
             // gradient's epilogue (the last layer has no ReLU behind its tap)
             if (kVggTap[i]) {
                 const float sc = 0.001f * kVggW[kVggTap[i] - 1] / (float)half;
-                TRY(launch_l1_fwd_bwd(T.va[i], T.va[i] + half, half, sc, dcur, i == 13 ? 0 : 1, T.cpartial,
-                                      loss_vgg_acc, st, gs * vgg_mul, i != 13));
+                TRY_RET(launch_l1_fwd_bwd(T.va[i], T.va[i] + half, half, sc, dcur, i == 13 ? 0 : 1, T.cpartial, loss_acc, st,
+                                          gs * vgg_mul, i != 13));
             }
-            if (i == 0 && prec == S3D_PREC_F16X3) {   // 64 -> 3 channels: a 1x1 product into 27 (channel, tap) planes + a nine-neighbour gather
-                ConvLaunch z = R.mk(T.w_vggZ, Nd, r, r, 1, nullptr, S3D_ACT_NONE);
-                z.nsrc = 1;
-                z.src[0] = plain_src(dcur, kVggCout[0]);
-                z.out = dnext;
-                TRY(launch_conv(z, st));
-                TRY(launch_vgg_first_bwd(dnext, V->std, T.drec, Nd, S, st));
+            if (i == 0 && R.prec == S3D_PREC_F16X3) {   // 64 -> 3 channels: a 1x1 product into 27 (channel, tap) planes + a nine-neighbour gather
+                TRY_RET(R.conv(T.w_vggZ, Nd, r, r, 1, dcur, kVggCout[0], dnext));
+                TRY_RET(launch_vgg_first_bwd(dnext, V->std, T.drec, Nd, S, st));
                 break;
             }
             // data gradient of conv i
@@ -1052,207 +1086,125 @@ static int train_step_impl(const S3dUNetParams* U, const S3dHeadParams* Hd, cons
                 c.gate = T.va[i - 1];
                 c.gate_scale = 1.f;
             }
-            TRY(launch_conv(c, st));
+            TRY_RET(launch_conv(c, st));
             if (i == 0) {
-                TRY(launch_vgg_prep_bwd(dnext, V->std, T.drec, Nd, S, st));
+                TRY_RET(launch_vgg_prep_bwd(dnext, V->std, T.drec, Nd, S, st));
             } else if (kVggPoolAfter[i - 1]) {
                 // input of conv i was pool(va[i-1]): route to the arg-max positions
-                TRY(launch_pool_bwd(T.va[i - 1], dnext, dcur, Nd, 2 * r, 2 * r, kVggCout[i - 1], st, mask_below));
-                --pi;
+                TRY_RET(launch_pool_bwd(T.va[i - 1], dnext, dcur, Nd, 2 * r, 2 * r, kVggCout[i - 1], st, mask_below));
             } else {
                 float* t = dcur; dcur = dnext; dnext = t;
             }
         }
-        (void)pi;
+        return 0;
     }
 
-    // =========================================================================================
-    // 5. decoder backward
-    // =========================================================================================
-    float* vec = T.vec;
-    range.next("s3d:train:decoder_bwd");
-    TRY(D.backward(T.X0, T.dsdf, nsdf));   // d X0 in T.dA
-    // ---- sampling backward: dA = d X0 ----
-    range.next("s3d:train:sample_bwd_and_head_grads");
-    for (int l = 0; l < 3; ++l) {
-        const size_t r = (size_t)r5 << l;
-        TRY(R.zero(T.dlat_proj[l], (size_t)Nd * r * r * 128));
+    // ---- 5. decoder backward ----
+    int decoder_backward() {
+        range.next("s3d:train:decoder_bwd");
+        return D.backward(T.X0, T.dsdf, d.nsdf);   // d X0 in T.dA
     }
-    for (int l = 0; l < 5; ++l) {
-        const size_t r = (size_t)r5 << l;
-        TRY(R.zero(T.dF[l], (size_t)Nd * r * r * lc[l]));
-    }
-    {
-        SampleBwdArgs sb = {};
-        sb.dX = T.dA;
-        for (int l = 0; l < 3; ++l) sb.dproj[l] = T.dlat_proj[l];
-        sb.dfine[0] = T.dF[3]; sb.dfine[1] = T.dF[4];
-        sb.ws34_t = T.ws34_t;
-        sb.ws34_t16 = prec == S3D_PREC_F16X3 ? T.ws34_t16 : nullptr;
-        sb.qry = batch->qry; sb.rot = batch->rot; sb.trans = batch->trans;
-        sb.flip_yz = 0; sb.size = S; sb.n_slices = ns;
-        sb.n_qry = Q; sb.groups_per_batch = gpb; sb.groups = G;
-        sb.perm = perm; sb.bin_ends = perm ? T.sortws : nullptr;
-        sb.gxy = perm ? T.gxy : nullptr;
-        sb.partial = perm ? T.sb_partial : nullptr;
-        TRY(launch_sample_bwd(sb, st));
-    }
-    // fc_s / fc_p parameter gradients
-    TRY(launch_tok0_copy(T.dA, T.dc1, G, Tn, 0, 128, st));                          // d token-0 rows
-    TRY(launch_colsum(T.dc1, rows0, 128, 0, 128, (float*)dH->fc_p_b, 0, T.cpartial, st));
-    {
-        WgradArgs wp = R.wg(T.dc1, 128, 128, plain_src(T.qrot4, 4), 4, 1, 1, (int)rows0, 1);
-        wp.out = vec; wp.out_kind = S3D_PACK_LINEAR; wp.ld = 4;                      // [128][4] -> [128][3]
-        TRY(launch_wgrad(wp, st));
-        TRY(launch_copy_cols(vec, (float*)dH->fc_p_w, 128, 4, 3, st));
-        WgradArgs ws = R.wg(T.dA, 128, 128, plain_src(T.raw34, 96), 96, 1, 1, (int)rows, 1);
-        ws.out = (float*)dH->fc_s_w + 896; ws.out_kind = S3D_PACK_LINEAR; ws.ld = 992;
-        ws.bias_out = (float*)dH->fc_s_b;                                            // column sums of all token rows ...
-        TRY(launch_wgrad(ws, st));
-        TRY(launch_axpy((float*)dH->fc_s_b, dH->fc_p_b, -1.f, 128, st));            // ... slice tokens only
-    }
-    // fc_s fold backward: dW_l = dG_l^T f_l ;  dF[l] += dG_l W_l
-    for (int l = 0; l < 3; ++l) {
-        const int r = r5 << l;
-        WgradArgs wf = R.wg(T.dlat_proj[l], 128, 128, plain_src(T.F[l], lc[l]), lc[l], Nd, r, r, 1);
-        wf.out = (float*)dH->fc_s_w + lo[l]; wf.out_kind = S3D_PACK_LINEAR; wf.ld = 992;
-        TRY(launch_wgrad(wf, st));
-        ConvLaunch c = R.mk(T.w_projT[l], Nd, r, r, 1, nullptr, S3D_ACT_NONE);
-        c.nsrc = 1;
-        c.src[0] = plain_src(T.dlat_proj[l], 128);
-        c.out = T.dF[l];
-        c.out_accumulate = 1;
-        TRY(launch_conv(c, st));
-    }
-    // Gradient buckets in the order the backward finishes them (data-parallel training all-reduces a bucket while the
-    // rest of the backward runs): each is rescaled by 1/gs as soon as it is final, then its event is recorded.
-    const float inv_gs = 1.f / gs;
-    {   // bucket 0: transformer decoder + fc_p / fc_s / fc_out
+
+    // ---- sampling backward (dA = d X0), the fc_p / fc_s gradients, and gradient bucket 0 ----
+    int sampler_backward_and_head_grads() {
+        range.next("s3d:train:sample_bwd_and_head_grads");
+        const int Nd = d.Nd, r5 = d.r5;
+        for (int l = 0; l < 3; ++l) {
+            const size_t r = (size_t)r5 << l;
+            TRY_RET(R.zero(T.dlat_proj[l], (size_t)Nd * r * r * 128));
+        }
+        for (int l = 0; l < 5; ++l) {
+            const size_t r = (size_t)r5 << l;
+            TRY_RET(R.zero(T.dF[l], (size_t)Nd * r * r * kLatC[l]));
+        }
+        {
+            SampleBwdArgs sb = sample_bwd_args(T.dA);
+            for (int l = 0; l < 3; ++l) sb.dproj[l] = T.dlat_proj[l];
+            sb.dfine[0] = T.dF[3]; sb.dfine[1] = T.dF[4];
+            sb.ws34_t = T.ws34_t;
+            sb.ws34_t16 = R.prec == S3D_PREC_F16X3 ? T.ws34_t16 : nullptr;
+            sb.partial = perm ? T.sb_partial : nullptr;
+            TRY_RET(launch_sample_bwd(sb, st));
+        }
+        // fc_s / fc_p parameter gradients
+        TRY_RET(launch_tok0_copy(T.dA, T.dc1, d.G, d.Tn, 0, 128, st));                          // d token-0 rows
+        TRY_RET(launch_colsum(T.dc1, d.rows0, 128, 0, 128, (float*)dH->fc_p_b, 0, T.cpartial, st));
+        TRY_RET(R.wgrad_xyz(T.dc1, 128, T.qrot4, d.rows0, dH->fc_p_w));
+        // (fc_s's bias gradient: the column sums of all token rows ...
+        TRY_RET(R.wgrad_lin(R.wg_rows(T.dA, 128, T.raw34, 96, d.rows), dH->fc_s_w + 896, 992, dH->fc_s_b));
+        TRY_RET(launch_axpy((float*)dH->fc_s_b, dH->fc_p_b, -1.f, 128, st));                   // ... slice tokens only)
+        // fc_s fold backward: dW_l = dG_l^T f_l ;  dF[l] += dG_l W_l
+        for (int l = 0; l < 3; ++l) {
+            const int r = r5 << l;
+            TRY_RET(R.wgrad_lin(R.wg(T.dlat_proj[l], 128, 128, plain_src(T.F[l], kLatC[l]), kLatC[l], Nd, r, r, 1),
+                                dH->fc_s_w + kFcsCol[l], 992));
+            TRY_RET(R.conv(T.w_projT[l], Nd, r, r, 1, T.dlat_proj[l], 128, T.dF[l], nullptr, S3D_ACT_NONE, 1));
+        }
+        // Gradient buckets in the order the backward finishes them (data-parallel training all-reduces a bucket while the
+        // rest of the backward runs): each is rescaled by 1/gs as soon as it is final, then its event is recorded.
+        // bucket 0: transformer decoder + fc_p / fc_s / fc_out
         ScaleTable tb;
         tb.count = 0;
         tb.add(dH->fc_p_w, 128 * 3); tb.add(dH->fc_p_b, 128);
         tb.add(dH->fc_s_w, 128 * 992); tb.add(dH->fc_s_b, 128);
         add_layer_grads(tb, dH->layer);
         tb.add(dH->fc_out_w, 128); tb.add(dH->fc_out_b, 1);
-        TRY(launch_scale_table(tb, inv_gs, st));
-        if (ev[0]) (void)hipEventRecord(ev[0], st);
+        TRY_RET(rescale(tb));
+        record(0);
+        return 0;
+    }
+    void record(int bucket) const {
+        if (batch->ev_grad_ready[bucket]) (void)hipEventRecord((hipEvent_t)batch->ev_grad_ready[bucket], st);
     }
 
-    // =========================================================================================
-    // 6. U-Net backward
-    // =========================================================================================
-    range.next("s3d:train:unet_bwd");
-    {   // OutConv: rec = tanh(W f4 + b)
-        float* dz16 = T.scrA;  // (Nd,S,S,16)
-        TRY(launch_tanh_bwd(rec, T.drec, dz16, Nd, 3, S, S, 16, st));
-        TRY(launch_colsum(dz16, (long)Nd * S * S, 16, 0, 16, vec, 0, T.cpartial, st));
-        TRY(R.copy((float*)dU->outc.b, vec, 3));
-        WgradArgs w = R.wg(dz16, 16, 3, plain_src(T.F[4], 32), 32, Nd, S, S, 1);
-        w.out = (float*)dU->outc.w; w.out_kind = S3D_PACK_LINEAR; w.ld = 32;
-        TRY(launch_wgrad(w, st));
-        ConvLaunch c = R.mk(T.w_outc_d, Nd, S, S, 1, nullptr, S3D_ACT_NONE);
-        c.nsrc = 1;
-        c.src[0] = plain_src(dz16, 16);
-        c.out = T.dF[4];
-        c.out_accumulate = 1;
-        TRY(launch_conv(c, st));
-    }
-    {
-        const int skc[5] = {64, 128, 256, 512, 512};
-        for (int k = 0; k < 5; ++k) TRY(R.zero(T.dskip[k], ((size_t)B * S * S >> (2 * k)) * skc[k]));
-    }
-    for (int i = 3; i >= 0; --i) {
-        const int C = kUpC[i], Ct = C / 2, rp = r5 << i, ro = rp * 2;
+    // ---- 6. U-Net backward ----
+    // one up block, F[i+1] -> F[i]: conv c2, conv c1 on cat([proj tiled, up]), trans_up, the transposed conv
+    int up_block_backward(int i) {
+        const int B = d.B, ns = d.ns, Nd = d.Nd;
+        const int C = kUpC[i], Ct = C / 2, rp = d.r5 << i, ro = rp * 2;
         float* g2 = T.scrA;     // dz2
         float* dmid = T.scrB;
         float* g1 = T.scrC;     // dz1
         float* dpt = T.scrD;    // d proj (tiled) / d up
         // F[i+1] = relu(bn2(z2))
-        TRY(launch_bn_bwd(T.z2[i], T.m2[i], T.r2[i], U->up_c2[i].bn[0], U->up_c2[i].bn[1], T.dF[i + 1], g2,
-                          (float*)dU->up_c2[i].bn[0], (float*)dU->up_c2[i].bn[1], Nd, ro, ro, Ct, 0, T.cpartial, st, nullptr,
-                          R.sync));
-        {
-            WgradArgs w = R.wg(g2, Ct, Ct, plain_src(T.mid[i], Ct), Ct, Nd, ro, ro, 3);
-            w.out = (float*)dU->up_c2[i].w; w.out_kind = S3D_PACK_CONV; w.cin_tot = Ct; w.cin_begin = 0;
-            TRY(launch_wgrad(w, st));
-            ConvLaunch c = R.mk(T.w_c2_d[i], Nd, ro, ro, 3, nullptr, S3D_ACT_NONE);
-            c.nsrc = 1;
-            c.src[0] = plain_src(g2, Ct);
-            c.out = dmid;
-            TRY(launch_conv(c, st));
-        }
+        TRY_RET(launch_bn_bwd(T.z2[i], T.m2[i], T.r2[i], U->up_c2[i].bn[0], U->up_c2[i].bn[1], T.dF[i + 1], g2,
+                              (float*)dU->up_c2[i].bn[0], (float*)dU->up_c2[i].bn[1], Nd, ro, ro, Ct, 0, T.cpartial, st, nullptr,
+                              R.sync));
+        TRY_RET(R.wgrad_conv(R.wg(g2, Ct, Ct, plain_src(T.mid[i], Ct), Ct, Nd, ro, ro, 3), dU->up_c2[i].w, Ct, 0));
+        TRY_RET(R.conv(T.w_c2_d[i], Nd, ro, ro, 3, g2, Ct, dmid));
         // mid = relu(bn1(z1))
-        TRY(launch_bn_bwd(T.z1[i], T.m1[i], T.r1[i], U->up_c1[i].bn[0], U->up_c1[i].bn[1], dmid, g1,
-                          (float*)dU->up_c1[i].bn[0], (float*)dU->up_c1[i].bn[1], Nd, ro, ro, Ct, 0, T.cpartial, st, nullptr,
-                          R.sync));
-        {   // conv c1 on cat([proj tiled, up])
-            WgradArgs wp = R.wg(g1, Ct, Ct, ConvSrc{T.proj[i], Ct, ns, 0, 0}, Ct, Nd, ro, ro, 3);
-            wp.out = (float*)dU->up_c1[i].w; wp.out_kind = S3D_PACK_CONV; wp.cin_tot = C; wp.cin_begin = 0;
-            TRY(launch_wgrad(wp, st));
-            WgradArgs wu = R.wg(g1, Ct, Ct, plain_src(T.up[i], Ct), Ct, Nd, ro, ro, 3);
-            wu.out = (float*)dU->up_c1[i].w; wu.out_kind = S3D_PACK_CONV; wu.cin_tot = C; wu.cin_begin = Ct;
-            TRY(launch_wgrad(wu, st));
-            // d proj (per slice image) -> sum over slices -> trans_up backward
-            ConvLaunch cp = R.mk(T.w_c1_dp[i], Nd, ro, ro, 3, nullptr, S3D_ACT_NONE);
-            cp.nsrc = 1;
-            cp.src[0] = plain_src(g1, Ct);
-            cp.out = dpt;
-            TRY(launch_conv(cp, st));
-            float* dproj = T.encA;   // (B,ro,ro,Ct)
-            TRY(launch_slice_sum(dpt, dproj, B, ns, (long)ro * ro * Ct, 0, st));
-            TRY(launch_colsum(dproj, (long)B * ro * ro, Ct, 0, Ct, (float*)dU->trans_up[i].b, 0, T.cpartial, st));
-            WgradArgs wt = R.wg(dproj, Ct, Ct, plain_src(T.z[kTapConv[3 - i]], C), C, B, ro, ro, 1);
-            wt.out = (float*)dU->trans_up[i].w; wt.out_kind = S3D_PACK_LINEAR; wt.ld = C;
-            TRY(launch_wgrad(wt, st));
-            ConvLaunch ct = R.mk(T.w_tup_d[i], B, ro, ro, 1, nullptr, S3D_ACT_NONE);
-            ct.nsrc = 1;
-            ct.src[0] = plain_src(dproj, Ct);
-            ct.out = T.dskip[3 - i];
-            ct.out_accumulate = 1;
-            TRY(launch_conv(ct, st));
-            // d up
-            ConvLaunch cu = R.mk(T.w_c1_du[i], Nd, ro, ro, 3, nullptr, S3D_ACT_NONE);
-            cu.nsrc = 1;
-            cu.src[0] = plain_src(g1, Ct);
-            cu.out = dpt;
-            TRY(launch_conv(cu, st));
-        }
-        {   // ConvTranspose2d backward: d up (Nd,ro,ro,Ct) -> dF[i] (Nd,rp,rp,C) (+=), dW [C][Ct][2][2], db
-            TRY(launch_colsum(dpt, (long)Nd * ro * ro, Ct, 0, Ct, (float*)dU->up_t[i].b, 0, T.cpartial, st));
-            ConvSrc dsrc = plain_src(dpt, Ct);
-            WgradArgs w = R.wg(T.F[i], C, C, dsrc, Ct, Nd, rp, rp, 2);
-            w.stride = 2; w.Hin = ro; w.Win = ro;
-            w.out = (float*)dU->up_t[i].w; w.out_kind = S3D_PACK_CONVT; w.ct = Ct;
-            TRY(launch_wgrad(w, st));
-            ConvLaunch c = R.mk(T.w_upt_d[i], Nd, rp, rp, 2, nullptr, S3D_ACT_NONE);
-            c.stride = 2; c.Hin = ro; c.Win = ro;
-            c.nsrc = 1;
-            c.src[0] = dsrc;
-            c.out = T.dF[i];
-            c.out_accumulate = 1;
-            TRY(launch_conv(c, st));
-        }
-    }
-    {   // trans_c backward: F[0] = W_a x5(tiled) + W_b emb + b
-        const long P0 = (long)Nd * r5 * r5;
-        TRY(launch_colsum(T.dF[0], P0, 512, 0, 512, (float*)dU->trans_c.b, 0, T.cpartial, st));
-        WgradArgs wa = R.wg(T.dF[0], 512, 512, ConvSrc{T.z[12], 512, ns, 0, 0}, 512, Nd, r5, r5, 1);
-        wa.out = (float*)dU->trans_c.w; wa.out_kind = S3D_PACK_LINEAR; wa.ld = 640;
-        TRY(launch_wgrad(wa, st));
-        WgradArgs wb = R.wg(T.dF[0], 512, 512, ConvSrc{U->emds, 128, 1, ns, 1}, 128, Nd, r5, r5, 1);
-        wb.out = (float*)dU->trans_c.w + 512; wb.out_kind = S3D_PACK_LINEAR; wb.ld = 640;
-        TRY(launch_wgrad(wb, st));
-        // d x5 = sum over slices of W_a^T dF0
-        ConvLaunch c = R.mk(T.w_transc_d, Nd, r5, r5, 1, nullptr, S3D_ACT_NONE);
+        TRY_RET(launch_bn_bwd(T.z1[i], T.m1[i], T.r1[i], U->up_c1[i].bn[0], U->up_c1[i].bn[1], dmid, g1,
+                              (float*)dU->up_c1[i].bn[0], (float*)dU->up_c1[i].bn[1], Nd, ro, ro, Ct, 0, T.cpartial, st, nullptr,
+                              R.sync));
+        // conv c1 on cat([proj tiled, up])
+        TRY_RET(R.wgrad_conv(R.wg(g1, Ct, Ct, ConvSrc{T.proj[i], Ct, ns, 0, 0}, Ct, Nd, ro, ro, 3), dU->up_c1[i].w, C, 0));
+        TRY_RET(R.wgrad_conv(R.wg(g1, Ct, Ct, plain_src(T.up[i], Ct), Ct, Nd, ro, ro, 3), dU->up_c1[i].w, C, Ct));
+        // d proj (per slice image) -> sum over slices -> trans_up backward
+        TRY_RET(R.conv(T.w_c1_dp[i], Nd, ro, ro, 3, g1, Ct, dpt));
+        float* dproj = T.encA;   // (B,ro,ro,Ct)
+        TRY_RET(launch_slice_sum(dpt, dproj, B, ns, (long)ro * ro * Ct, 0, st));
+        TRY_RET(launch_colsum(dproj, (long)B * ro * ro, Ct, 0, Ct, (float*)dU->trans_up[i].b, 0, T.cpartial, st));
+        TRY_RET(R.wgrad_lin(R.wg(dproj, Ct, Ct, plain_src(T.z[kTapConv[3 - i]], C), C, B, ro, ro, 1), dU->trans_up[i].w, C));
+        TRY_RET(R.conv(T.w_tup_d[i], B, ro, ro, 1, dproj, Ct, T.dskip[3 - i], nullptr, S3D_ACT_NONE, 1));
+        // d up
+        TRY_RET(R.conv(T.w_c1_du[i], Nd, ro, ro, 3, g1, Ct, dpt));
+        // ConvTranspose2d backward: d up (Nd,ro,ro,Ct) -> dF[i] (Nd,rp,rp,C) (+=), dW [C][Ct][2][2], db
+        TRY_RET(launch_colsum(dpt, (long)Nd * ro * ro, Ct, 0, Ct, (float*)dU->up_t[i].b, 0, T.cpartial, st));
+        ConvSrc dsrc = plain_src(dpt, Ct);
+        WgradArgs w = R.wg(T.F[i], C, C, dsrc, Ct, Nd, rp, rp, 2);
+        w.stride = 2; w.Hin = ro; w.Win = ro;
+        w.out = (float*)dU->up_t[i].w; w.out_kind = S3D_PACK_CONVT; w.ct = Ct;
+        TRY_RET(launch_wgrad(w, st));
+        ConvLaunch c = R.mk(T.w_upt_d[i], Nd, rp, rp, 2, nullptr, S3D_ACT_NONE);
+        c.stride = 2; c.Hin = ro; c.Win = ro;
         c.nsrc = 1;
-        c.src[0] = plain_src(T.dF[0], 512);
-        c.out = T.scrA;
-        TRY(launch_conv(c, st));
-        TRY(launch_slice_sum(T.scrA, T.dskip[4], B, ns, (long)r5 * r5 * 512, 1, st));
-        // d emds[s][e] = sum over batch and pixels of (W_b^T dF0)[b*ns+s]: column sums of dF0 per slice, times W_b
-        TRY(launch_emb_grad(T.dF[0], U->trans_c.w, (float*)dU->emds, B, ns, r5 * r5, st));
+        c.src[0] = dsrc;
+        c.out = T.dF[i];
+        c.out_accumulate = 1;
+        return launch_conv(c, st);
     }
-    {   // bucket 1: the U-Net's decoder half (trans_c, up1..4, trans_up1..4, outc, slice embeddings)
+    // bucket 1: the U-Net's decoder half (trans_c, up1..4, trans_up1..4, outc, slice embeddings)
+    int close_unet_decoder_bucket() {
         ScaleTable tb;
         tb.count = 0;
         tb.add(dU->trans_c.w, 512 * 640); tb.add(dU->trans_c.b, 512);
@@ -1264,19 +1216,65 @@ static int train_step_impl(const S3dUNetParams* U, const S3dHeadParams* Hd, cons
             tb.add(dU->up_c2[i].w, Ct * Ct * 9); tb.add(dU->up_c2[i].bn[0], Ct); tb.add(dU->up_c2[i].bn[1], Ct);
         }
         tb.add(dU->outc.w, 3 * 32); tb.add(dU->outc.b, 3);
-        tb.add(dU->emds, (long)ns * 128);
-        TRY(launch_scale_table(tb, inv_gs, st));
-        if (ev[1]) (void)hipEventRecord(ev[1], st);
+        tb.add(dU->emds, (long)d.ns * 128);
+        TRY_RET(rescale(tb));
+        record(1);
+        return 0;
     }
-    // bucket 2 (encoder convs 7..12 + their BatchNorms) is closed inside enc_backward; bucket 3 = the shallow rest
-    TRY(enc_backward(R, U->enc, dU->enc, B, S, ev[2], inv_gs));
-    {
+    int unet_backward() {
+        range.next("s3d:train:unet_bwd");
+        const int B = d.B, S = d.S, ns = d.ns, Nd = d.Nd, r5 = d.r5;
+        {   // OutConv: rec = tanh(W f4 + b)
+            float* dz16 = T.scrA;  // (Nd,S,S,16)
+            TRY_RET(launch_tanh_bwd(rec, T.drec, dz16, Nd, 3, S, S, 16, st));
+            TRY_RET(launch_colsum(dz16, (long)Nd * S * S, 16, 0, 16, T.vec, 0, T.cpartial, st));
+            TRY_RET(R.copy((float*)dU->outc.b, T.vec, 3));
+            TRY_RET(R.wgrad_lin(R.wg(dz16, 16, 3, plain_src(T.F[4], 32), 32, Nd, S, S, 1), dU->outc.w, 32));
+            TRY_RET(R.conv(T.w_outc_d, Nd, S, S, 1, dz16, 16, T.dF[4], nullptr, S3D_ACT_NONE, 1));
+        }
+        {
+            const int skc[5] = {64, 128, 256, 512, 512};
+            for (int k = 0; k < 5; ++k) TRY_RET(R.zero(T.dskip[k], ((size_t)B * S * S >> (2 * k)) * skc[k]));
+        }
+        for (int i = 3; i >= 0; --i) TRY_RET(up_block_backward(i));
+        {   // trans_c backward: F[0] = W_a x5(tiled) + W_b emb + b
+            const long P0 = (long)Nd * r5 * r5;
+            TRY_RET(launch_colsum(T.dF[0], P0, 512, 0, 512, (float*)dU->trans_c.b, 0, T.cpartial, st));
+            TRY_RET(R.wgrad_lin(R.wg(T.dF[0], 512, 512, ConvSrc{T.z[12], 512, ns, 0, 0}, 512, Nd, r5, r5, 1), dU->trans_c.w, 640));
+            TRY_RET(R.wgrad_lin(R.wg(T.dF[0], 512, 512, ConvSrc{U->emds, 128, 1, ns, 1}, 128, Nd, r5, r5, 1),
+                                dU->trans_c.w + 512, 640));
+            // d x5 = sum over slices of W_a^T dF0
+            TRY_RET(R.conv(T.w_transc_d, Nd, r5, r5, 1, T.dF[0], 512, T.scrA));
+            TRY_RET(launch_slice_sum(T.scrA, T.dskip[4], B, ns, (long)r5 * r5 * 512, 1, st));
+            // d emds[s][e] = sum over batch and pixels of (W_b^T dF0)[b*ns+s]: column sums of dF0 per slice, times W_b
+            TRY_RET(launch_emb_grad(T.dF[0], U->trans_c.w, (float*)dU->emds, B, ns, r5 * r5, st));
+        }
+        TRY_RET(close_unet_decoder_bucket());
+        // bucket 2 (encoder convs 7..12 + their BatchNorms) is closed inside enc_backward; bucket 3 = the shallow rest
+        TRY_RET(enc_backward(R, U->enc, dU->enc, B, S, (hipEvent_t)batch->ev_grad_ready[2], 1.f / gs));
         ScaleTable tb;
         tb.count = 0;
         add_enc_grads_range(tb, dU->enc, 0, 7);
-        TRY(launch_scale_table(tb, inv_gs, st));
+        return rescale(tb);
     }
-    return 0;
+
+    int forward() {
+        TRY_RET(unet_forward());
+        TRY_RET(tokens_and_decoder_forward());
+        return vgg_forward();
+    }
+    int backward() {
+        TRY_RET(decoder_backward());
+        TRY_RET(sampler_backward_and_head_grads());
+        return unet_backward();
+    }
+};
+
+static int open_reg_step(const char* who, bool pointers_ok, int B, int S, long Q, int ns, float dropout_p, int prec,
+                         void* workspace, size_t workspace_bytes, StepDims& d, TrainBufs& T) {
+    return open_step(who, pointers_ok, B, S, Q, ns, dropout_p, prec,
+                     prec == S3D_PREC_F32 || prec == S3D_PREC_F16X3 || prec == S3D_PREC_F16, workspace, workspace_bytes, d, T,
+                     nullptr);
 }
 
 extern "C" int s3d_train_fwd_bwd(const S3dUNetParams* U, const S3dHeadParams* Hd, const S3dVggParams* V,
@@ -1284,8 +1282,17 @@ extern "C" int s3d_train_fwd_bwd(const S3dUNetParams* U, const S3dHeadParams* Hd
                                  int B, int S, long Q, int ns, float dropout_p, unsigned long long seed, int prec,
                                  float* losses_out, float* sdf_pred_out, float* slices_rec_out, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-    return train_step_impl(U, Hd, V, dU, dH, batch, B, S, Q, ns, dropout_p, seed, prec, losses_out, sdf_pred_out,
-                           slices_rec_out, workspace, workspace_bytes, stream, PH_FWD | PH_LOSS | PH_BWD, nullptr);
+    StepDims d;
+    TrainBufs T = {};
+    TRY(open_reg_step("train", U && Hd && V && dU && dH && batch && losses_out, B, S, Q, ns, dropout_p, prec, workspace,
+                      workspace_bytes, d, T));
+    RegStep s(U, Hd, V, dU, dH, batch, d, T, dropout_p, seed, prec, sdf_pred_out, slices_rec_out, stream);
+    TRY(s.R.zero(losses_out, 4));
+    TRY(s.pack_weights());
+    TRY(s.forward());
+    TRY(s.reference_loss_grads(losses_out));
+    TRY(s.vgg_backward(losses_out + 2, 1.f));
+    return s.backward();
 }
 
 extern "C" int s3d_train_fwd(const S3dUNetParams* U, const S3dHeadParams* Hd, const S3dVggParams* V,
@@ -1293,19 +1300,15 @@ extern "C" int s3d_train_fwd(const S3dUNetParams* U, const S3dHeadParams* Hd, co
                              unsigned long long seed, int prec, float* vgg_loss_out, float* sdf_pred_out,
                              float* slices_rec_out, void* workspace, size_t workspace_bytes, void* stream) {
     S3D_CHECK_ARG(vgg_loss_out && sdf_pred_out && slices_rec_out, "train_fwd: null output");
-    Arena A{(float*)workspace, 0};
-    TrainBufs T;
-    if (workspace && B >= 1 && S >= 16 && Q >= 1 && ns >= 1) plan_train(A, B, S, Q, ns, T);
-    else return train_step_impl(U, Hd, V, nullptr, nullptr, batch, B, S, Q, ns, dropout_p, seed, prec, nullptr,
-                                sdf_pred_out, slices_rec_out, workspace, workspace_bytes, stream, PH_FWD, nullptr);
-    if (workspace_bytes < A.off * sizeof(float)) {
-        s3d_set_error("train_fwd: workspace %zu < %zu bytes", workspace_bytes, A.off * sizeof(float));
-        return S3D_E_WORKSPACE;
-    }
-    float* losses = T.vec + 8000;    // [loss_pred, loss_img, loss_vgg, acc] scratch beyond the small-vector uses of T.vec
-    TRY(train_step_impl(U, Hd, V, nullptr, nullptr, batch, B, S, Q, ns, dropout_p, seed, prec, losses, sdf_pred_out,
-                        slices_rec_out, workspace, workspace_bytes, stream, PH_FWD, nullptr));
-    if (hipMemcpyAsync(vgg_loss_out, losses + 2, sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+    StepDims d;
+    TrainBufs T = {};
+    TRY(open_reg_step("train_fwd", U && Hd && V && batch, B, S, Q, ns, dropout_p, prec, workspace, workspace_bytes, d, T));
+    RegStep s(U, Hd, V, nullptr, nullptr, batch, d, T, dropout_p, seed, prec, sdf_pred_out, slices_rec_out, stream);
+    TRY(s.R.zero(T.fwd_losses, 4));
+    TRY(s.pack_weights());
+    TRY(s.forward());
+    TRY(s.vgg_loss_value(T.fwd_losses + 2));
+    if (hipMemcpyAsync(vgg_loss_out, T.fwd_losses + 2, sizeof(float), hipMemcpyDeviceToDevice, s.st) != hipSuccess) {
         s3d_set_error("train_fwd: copy of vgg_loss failed");
         return S3D_E_ARG;
     }
@@ -1318,11 +1321,15 @@ extern "C" int s3d_train_bwd(const S3dUNetParams* U, const S3dHeadParams* Hd, co
                              const float* d_sdf_pred, const float* d_slices_rec, float d_vgg_loss, float grad_scale,
                              float* slices_rec, void* workspace, size_t workspace_bytes, void* stream) {
     S3D_CHECK_ARG(slices_rec, "train_bwd: slices_rec (the forward's output) is NULL");
-    S3D_CHECK_ARG(workspace, "train_bwd: null workspace");
-    TrainExt ext = {d_sdf_pred, d_slices_rec, d_vgg_loss, grad_scale};
-    float* losses = (float*)workspace;   // never written in this phase combination (kept non-NULL for the checks)
-    return train_step_impl(U, Hd, V, dU, dH, batch, B, S, Q, ns, dropout_p, seed, prec, losses, nullptr, slices_rec,
-                           workspace, workspace_bytes, stream, PH_BWD, &ext);
+    StepDims d;
+    TrainBufs T = {};
+    TRY(open_reg_step("train_bwd", U && Hd && V && dU && dH && batch, B, S, Q, ns, dropout_p, prec, workspace,
+                      workspace_bytes, d, T));
+    RegStep s(U, Hd, V, dU, dH, batch, d, T, dropout_p, seed, prec, nullptr, slices_rec, stream);
+    TRY(s.external_loss_grads(TrainExt{d_sdf_pred, d_slices_rec, d_vgg_loss, grad_scale}));
+    // (the tap kernels also sum the loss: into scratch here)
+    if (d_vgg_loss != 0.f) TRY(s.vgg_backward(T.vec, d_vgg_loss));
+    return s.backward();
 }
 
 // dropout mask as the kernels generate it: out[i] = keep(seed, site, idx0 + i) ? 1/(1-p) : 0   (testing hook)

@@ -859,3 +859,67 @@ def test_single_pass_f16_training_mode_tracks_the_split_precision_step():
     assert end["f16"] == end["f16"] and abs(end["f16"] - end["f16x3"]) < 0.1 * abs(end["f16x3"]), end
     print("single-pass f16 training mode: worst gradient deviation %.2e (%s), median %.2e; loss_pred after 20 steps %.4f vs %.4f"
           % (dev[-1][0], dev[-1][1], dev[len(dev) // 2][0], end["f16"], end["f16x3"]))
+
+
+def test_train_entry_points_reject_bad_arguments():
+    """The argument checks that open s3d_train_fwd_bwd, s3d_train_fwd, s3d_train_bwd and s3d_gt_train_fwd_bwd, through raw ctypes
+    calls with one fault at a time on otherwise valid arguments: a NULL parameter struct, a size that is no multiple of 16, dropout
+    1.0 and an unknown precision are S3D_E_ARG, a workspace one byte short is S3D_E_WORKSPACE; so are a NULL output of the forward
+    half and a NULL slices_rec of the backward half.  Every case returns before anything is launched."""
+    import ctypes as C
+    from slice3d_amd import _lib
+    from slice3d_amd.models import data_ptr, vgg_params
+    from slice3d_amd.models_gt import Slices3DGTModel
+    from slice3d_amd.synth import make_feed_dict
+    from slice3d_amd.trainer import HipGtTrainer
+    from slice3d_amd.weights import load_seeded
+    E_ARG, E_WS = -1, -2
+    b, s, q, ns = 1, 32, 16, 12
+    fd = make_feed_dict(b, s, q, ns, seed=1, device="cuda")
+    m, tr = make_trainer(ns)
+    mg = load_seeded(Slices3DGTModel(n_slices=ns, mode="train"), 0).cuda()
+    tg = HipGtTrainer(mg)
+    lib, dev = tr.lib, tr.grad_flat.device
+    st = _lib.stream_ptr(dev)
+    (u, h), v = tr._structs(data_ptr), vgg_params(m, data_ptr)
+    du, dh = tr._structs(tr._gptr)
+    ge, gh = tg._structs(data_ptr)
+    dge, dgh = tg._structs(tg._gptr)
+    tb = tr._batch_struct(tr._batch(fd, ("img_input", "img_slices", "qry_norot", "obj_rot_mat", "trans_mat_wo_rot_tp", "sdf")))
+    need = {"reg": lib.s3d_train_workspace_bytes(b, s, q, ns), "gt": lib.s3d_gt_train_workspace_bytes(b, s, q, ns)}
+    # large enough for S = 40 too, so that no call can be refused for its workspace before its size is looked at
+    nws = max(max(need.values()), lib.s3d_train_workspace_bytes(b, 40, q, ns), lib.s3d_gt_train_workspace_bytes(b, 40, q, ns))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    losses = torch.zeros(4, device=dev)
+    vgg = torch.zeros((), device=dev)
+    sdf = torch.zeros(b, q, device=dev)
+    rec = torch.zeros(b * ns, 3, s, s, device=dev)
+    P = lambda x: C.byref(x)
+
+    def fused(U=P(u), S=s, p=0.1, prec=_lib.PREC_F32, n=nws):
+        return lib.s3d_train_fwd_bwd(U, P(h), P(v), P(du), P(dh), P(tb), b, S, q, ns, p, 1, prec, losses.data_ptr(),
+                                     sdf.data_ptr(), rec.data_ptr(), ws.data_ptr(), n, st)
+
+    def fwd(U=P(u), S=s, p=0.1, prec=_lib.PREC_F32, n=nws, out=sdf.data_ptr()):
+        return lib.s3d_train_fwd(U, P(h), P(v), P(tb), b, S, q, ns, p, 1, prec, vgg.data_ptr(), out, rec.data_ptr(),
+                                 ws.data_ptr(), n, st)
+
+    def bwd(U=P(u), S=s, p=0.1, prec=_lib.PREC_F32, n=nws, slices_rec=rec.data_ptr()):
+        return lib.s3d_train_bwd(U, P(h), P(v), P(du), P(dh), P(tb), b, S, q, ns, p, 1, prec, sdf.data_ptr(), None, 0.0, 0.0,
+                                 slices_rec, ws.data_ptr(), n, st)
+
+    def gt(U=P(ge), S=s, p=0.1, prec=_lib.PREC_F32, n=nws):
+        return lib.s3d_gt_train_fwd_bwd(U, P(gh), P(dge), P(dgh), P(tb), b, S, q, ns, p, 1, prec, losses.data_ptr(),
+                                        sdf.data_ptr(), ws.data_ptr(), n, st)
+
+    for name, call, size in (("s3d_train_fwd_bwd", fused, need["reg"]), ("s3d_train_fwd", fwd, need["reg"]),
+                             ("s3d_train_bwd", bwd, need["reg"]), ("s3d_gt_train_fwd_bwd", gt, need["gt"])):
+        assert call(U=None) == E_ARG and b"null" in lib.s3d_last_error().lower(), name
+        assert call(S=40) == E_ARG, name
+        assert call(p=1.0) == E_ARG, name
+        assert call(prec=7) == E_ARG, name
+        assert call(n=size - 1) == E_WS, name
+    assert fwd(out=None) == E_ARG
+    assert bwd(slices_rec=None) == E_ARG
+    torch.cuda.synchronize()
+    assert float(losses.abs().sum()) == 0.0      # nothing ran
