@@ -155,7 +155,14 @@ struct EncLayout {
 };
 struct UNetLayout {
     EncLayout E;
-    PackedConv trans_c, trans_up[4], up_t[4], up_c1[4], up_c2[4], outc;
+    PackedConv trans_up[4], up_t[4], up_c1[4], up_c2[4], outc;
+    // trans_c by input-channel range: the 512 image channels (its shift = the bias) and the 128 slice-embedding channels
+    PackedConv trans_cx, trans_ce;
+    size_t slice_v;     // [ns][512]: v[s] = trans_c's embedding columns . emds[s] + bias, the per-slice part of the latent
+    size_t up1_tab;     // [ns][4][4][256]: up1's first 3x3 (up half) over ConvT(a map of v[s]) + bias, raw: one value per
+                        // (first | odd | even | last) row and column class — the per-slice part of up1's first pre-activation
+    size_t up1_tab_in;  // [ns][4][4][256]: that ConvT output (scratch of the pack)
+    PackedConv up_c1s[4];   // the skip half of up_c1's input channels as an image of its own (weights only); up_c1 holds the up half and the BN
     size_t emds;
     size_t enc0_raw;   // conv1_1's weight as is, (64,3,3,3): the 3-channel first layer runs a direct fp32 kernel on the NCHW image
     size_t total;
@@ -179,6 +186,13 @@ struct ImageAlloc {
         pc.scale = take(cout_pad);
         pc.shift = take(cout_pad);
     }
+    void weights(PackedConv& pc, int cout_pad, int KU) {   // a raw product: no epilogue vectors
+        pc.cout_pad = cout_pad;
+        pc.KU = KU;
+        pc.w = take((size_t)cout_pad * KU * 16);
+        pc.w16 = take((size_t)cout_pad * KU * 16);
+        pc.scale = pc.shift = 0;
+    }
 };
 
 static EncLayout enc_layout(ImageAlloc& a) {
@@ -196,12 +210,17 @@ static UNetLayout unet_layout(int n_slices) {
     UNetLayout L;
     ImageAlloc a;
     L.E = enc_layout(a);
-    a.conv(L.trans_c, 512, 640 / 16);
+    a.conv(L.trans_cx, 512, 512 / 16);
+    a.weights(L.trans_ce, 512, 128 / 16);
+    L.slice_v = a.take((size_t)n_slices * 512);
+    L.up1_tab = a.take((size_t)n_slices * 16 * 256);
+    L.up1_tab_in = a.take((size_t)n_slices * 16 * 256);
     for (int i = 0; i < 4; ++i) {
         const int C = kUpC[i], Ct = C / 2;
         a.conv(L.trans_up[i], Ct, C / 16);
         a.conv(L.up_t[i], 4 * Ct, C / 16);
-        a.conv(L.up_c1[i], Ct, 2 * 9 * Ct / 16);
+        a.weights(L.up_c1s[i], Ct, 9 * Ct / 16);
+        a.conv(L.up_c1[i], Ct, 9 * Ct / 16);
         a.conv(L.up_c2[i], Ct, 9 * Ct / 16);
     }
     a.conv(L.outc, 16, 32 / 16);
@@ -256,6 +275,8 @@ static int pack_encoder(const S3dConvParams P[13], float* base, const EncLayout&
     return 0;
 }
 
+static int pack_unet_slice_terms(float* base, const UNetLayout& L, int ns, hipStream_t st);   // (after conv_desc)
+
 extern "C" int s3d_unet_pack(const S3dUNetParams* P, void* packed, size_t packed_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     S3D_CHECK_ARG(P && packed, "unet_pack: null argument");
@@ -271,9 +292,10 @@ extern "C" int s3d_unet_pack(const S3dUNetParams* P, void* packed, size_t packed
         s3d_set_error("unet_pack: copy of conv1_1's weight failed");
         return S3D_E_ARG;
     }
-    TRY(pack_linear(P->trans_c.w, base + L.trans_c.w, 512, 512, 640, 640, 0, st));
-    TRY(pack_linear(P->trans_c.w, base + L.trans_c.w16, 512, 512, 640, 640, 0, st, 1));
-    TRY(launch_fold_bn(P->trans_c.b, nullptr, base + L.trans_c.scale, base + L.trans_c.shift, 512, 512, 1, 0, st));
+    TRY(pack_linear(P->trans_c.w, base + L.trans_cx.w, 512, 512, 512, 640, 0, st));
+    TRY(pack_linear(P->trans_c.w, base + L.trans_cx.w16, 512, 512, 512, 640, 0, st, 1));
+    TRY(launch_fold_bn(P->trans_c.b, nullptr, base + L.trans_cx.scale, base + L.trans_cx.shift, 512, 512, 1, 0, st));
+    TRY(pack_linear(P->trans_c.w + 512, base + L.trans_ce.w, 512, 512, 128, 640, 0, st));
     for (int i = 0; i < 4; ++i) {
         const int C = kUpC[i], Ct = C / 2;
         TRY(pack_linear(P->trans_up[i].w, base + L.trans_up[i].w, Ct, Ct, C, C, 0, st));
@@ -291,11 +313,12 @@ extern "C" int s3d_unet_pack(const S3dUNetParams* P, void* packed, size_t packed
             TRY(launch_fold_bn(P->up_t[i].b, nullptr, base + L.up_t[i].scale, base + L.up_t[i].shift, Ct, 4 * Ct, 4,
                                0, st));
         }
-        // DoubleConv conv0 on cat([skip_proj, up]) (unet_parts.py:73): two K segments
-        TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1[i].w, Ct, Ct, C, 0, Ct, L.up_c1[i].KU, 0, 9, st));
-        TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1[i].w, Ct, Ct, C, Ct, Ct, L.up_c1[i].KU, 9 * Ct / 16, 9, st));
-        TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1[i].w16, Ct, Ct, C, 0, Ct, L.up_c1[i].KU, 0, 9, st, 1));
-        TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1[i].w16, Ct, Ct, C, Ct, Ct, L.up_c1[i].KU, 9 * Ct / 16, 9, st, 1));
+        // DoubleConv conv0 on cat([skip_proj, up]) (unet_parts.py:73): the two halves of its input channels are two weight
+        // images, because the skip half's products are the same for every slice of an image (s3d_unet_encode_fwd)
+        TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1s[i].w, Ct, Ct, C, 0, Ct, L.up_c1s[i].KU, 0, 9, st));
+        TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1[i].w, Ct, Ct, C, Ct, Ct, L.up_c1[i].KU, 0, 9, st));
+        TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1s[i].w16, Ct, Ct, C, 0, Ct, L.up_c1s[i].KU, 0, 9, st, 1));
+        TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1[i].w16, Ct, Ct, C, Ct, Ct, L.up_c1[i].KU, 0, 9, st, 1));
         TRY(launch_fold_bn(nullptr, P->up_c1[i].bn, base + L.up_c1[i].scale, base + L.up_c1[i].shift, Ct, Ct, 1, 0,
                            st));
         TRY(pack_conv3(P->up_c2[i].w, base + L.up_c2[i].w, Ct, Ct, Ct, 0, Ct, L.up_c2[i].KU, 0, 9, st));
@@ -312,12 +335,13 @@ extern "C" int s3d_unet_pack(const S3dUNetParams* P, void* packed, size_t packed
         s3d_set_error("unet_pack: memcpy failed: %s", hipGetErrorString(e));
         return (int)e;
     }
-    return 0;
+    return pack_unet_slice_terms(base, L, P->n_slices, st);
 }
 
 #define S3D_SPLITK_FLOATS ((size_t)4718592)
 struct UNetWs {
-    size_t in16, a, b, x[5], p[4], proj, up, mid, splitk;
+    size_t in16, a, b, x[5], p[4], proj, pre, up, mid, splitk;
+    size_t lat, up1_u, up1_pre;   // per-image terms of the latent and of up1
     size_t total;
 };
 static UNetWs unet_ws(int B, int S, int ns) {
@@ -336,9 +360,13 @@ static UNetWs unet_ws(int B, int S, int ns) {
     for (int i = 0; i < 5; ++i) W.x[i] = take((px >> (2 * i)) * xc[i]);
     for (int i = 0; i < 4; ++i) W.p[i] = take((px >> (2 * (i + 1))) * xc[i]);
     W.proj = take(px * 32);                 // largest skip projection: (B,S,S,32)
+    W.pre = take(px * 32);                  // its 3x3 products, the per-image term of up_c1: same shape
     W.up = take(px * ns * 32);              // largest ConvT output: (B*ns,S,S,32)
     W.mid = take(px * ns * 32);
     W.splitk = take(S3D_SPLITK_FLOATS);   // split-K partials of the few-pixel encoder layers
+    W.lat = take(px / 256 * 512);         // trans_c over the image channels: (B,S/16,S/16,512)
+    W.up1_u = take(px / 64 * 256);        // its ConvT: (B,S/8,S/8,256)
+    W.up1_pre = take(px / 64 * 256);      // up1's first 3x3 over [skip, that]: same shape
     W.total = off;
     return W;
 }
@@ -375,6 +403,38 @@ static ConvLaunch proj_desc(const float* w, const void* w16, bool single, int n,
     c.src[0] = plain_src(x, k);
     c.out = out;
     return c;
+}
+
+static int pack_unet_slice_terms(float* base, const UNetLayout& L, int ns, hipStream_t st) {
+    // The weights-only terms of the decoder, with the engine's own launches in its exact fp32 mode (they are part of the packed
+    // image: a repack rebuilds them).  The slice embedding enters the latent as a spatially constant vector per slice, and
+    // nothing non-linear sits between trans_c and up1's first BatchNorm:
+    {   // v[s] = Wc_e . emds[s] + bias
+        ConvLaunch c = conv_desc(base, L.trans_ce, S3D_PREC_F32, ns, 1, 1, 1, S3D_ACT_NONE);
+        c.scale = nullptr; c.shift = base + L.trans_cx.shift;
+        c.nsrc = 1;
+        c.src[0] = plain_src(base + L.emds, 128);
+        c.out = base + L.slice_v;
+        TRY(launch_conv(c, st));
+    }
+    {   // ConvT of a constant map of v[s] (+ its bias): 2 x 2 -> 4 x 4 holds every (row class, column class) of any map size
+        ConvLaunch c = conv_desc(base, L.up_t[0], S3D_PREC_F32, ns, 2, 2, 1, S3D_ACT_NONE);
+        c.nsrc = 1;
+        c.src[0] = ConvSrc{base + L.slice_v, 512, 1, 0, 1};
+        c.out = base + L.up1_tab_in;
+        c.out_mode = S3D_OUT_CONVT;
+        c.cout_store = 256;
+        TRY(launch_conv(c, st));
+    }
+    {   // the up half of up1's first 3x3 over it, zero padded, raw
+        ConvLaunch c = conv_desc(base, L.up_c1[0], S3D_PREC_F32, ns, 4, 4, 3, S3D_ACT_NONE);
+        c.scale = c.shift = nullptr;
+        c.nsrc = 1;
+        c.src[0] = plain_src(base + L.up1_tab_in, 256);
+        c.out = base + L.up1_tab;
+        TRY(launch_conv(c, st));
+    }
+    return 0;
 }
 
 // VGG16-BN encoder (unet_custom.py:43-47, vgg16bn_feats.py:42-57) on N images of S x S, from conv `first` on: `in` is
@@ -440,14 +500,16 @@ extern "C" int s3d_unet_encode_fwd(const void* packed, const float* img, const S
     TRY(encoder_fwd(base, L.E, prec, B, S, 1, pp[0], tap, pp, pool, ws + W.splitk, st));
     // ---- latent = trans_c(cat[tile(x5), emb])  (unet_custom.py:50-58) ----
     const int r5 = S / 16;
+    // latent[b,s] = A[b] + v[s]: the image channels' products once per image, the slice embedding's (+ bias) from the pack
     {
-        ConvLaunch c = conv_desc(base, L.trans_c, prec, B * ns, r5, r5, 1, S3D_ACT_NONE);
-        c.nsrc = 2;
-        c.src[0] = ConvSrc{ws + W.x[4], 512, ns, 0, 0};
-        c.src[1] = ConvSrc{base + L.emds, 128, 1, ns, 1};
-        c.out = out->level[0];
+        ConvLaunch c = conv_desc(base, L.trans_cx, prec, B, r5, r5, 1, S3D_ACT_NONE);
+        c.scale = c.shift = nullptr;
+        c.nsrc = 1;
+        c.src[0] = plain_src(ws + W.x[4], 512);
+        c.out = ws + W.lat;
         TRY(launch_conv(c, st));
     }
+    TRY(launch_slice_bcast_add(ws + W.lat, base + L.slice_v, out->level[0], B, ns, (long)r5 * r5, 512, st));
     // ---- up1..up4 (unet_custom.py:60-67, unet_parts.py:55-75) ----
     const float* prev = out->level[0];
     int rp = r5;
@@ -460,22 +522,58 @@ extern "C" int s3d_unet_encode_fwd(const void* packed, const float* img, const S
             c.out = ws + W.proj;
             TRY(launch_conv(c, st));
         }
-        {  // ConvTranspose2d 2x2 s2 as a 1x1 GEMM with N = 4*Ct and a quadrant-scatter store
-            ConvLaunch c = conv_desc(base, L.up_t[i], prec, B * ns, rp, rp, 1, S3D_ACT_NONE);
+        {  // DoubleConv conv0 on cat([skip, up]): the skip half's products do not depend on the slice — raw, once per image.
+           // No split-K workspace: the split count depends on the batch, and the bits of an image must not
+            ConvLaunch c = conv_desc(base, L.up_c1s[i], prec, B, ro, ro, 3, S3D_ACT_NONE);
+            c.scale = c.shift = nullptr;
             c.nsrc = 1;
-            c.src[0] = plain_src(prev, C);
-            c.out = ws + W.up;
-            c.out_mode = S3D_OUT_CONVT;
-            c.cout_store = Ct;
+            c.src[0] = plain_src(ws + W.proj, Ct);
+            c.out = ws + W.pre;
             TRY(launch_conv(c, st));
         }
-        {
-            ConvLaunch c = conv_desc(base, L.up_c1[i], prec, B * ns, ro, ro, 3, S3D_ACT_RELU);
-            c.nsrc = 2;
-            c.src[0] = ConvSrc{ws + W.proj, Ct, ns, 0, 0};
-            c.src[1] = plain_src(ws + W.up, Ct);
-            c.out = ws + W.mid;
-            TRY(launch_conv(c, st));
+        if (i == 0) {
+            // up1 has no per-slice matrix work in front of its first BatchNorm: ConvT and the 3x3 are linear, so its first
+            // pre-activation is  P[b] + T[s][row class][column class]  with P = conv3x3(cat[skip, ConvT(A[b]) without bias])
+            // and T the pack's table (UNetLayout::up1_tab)
+            {
+                ConvLaunch c = conv_desc(base, L.up_t[0], prec, B, rp, rp, 1, S3D_ACT_NONE);
+                c.scale = c.shift = nullptr;
+                c.nsrc = 1;
+                c.src[0] = plain_src(ws + W.lat, C);
+                c.out = ws + W.up1_u;
+                c.out_mode = S3D_OUT_CONVT;
+                c.cout_store = Ct;
+                TRY(launch_conv(c, st));
+            }
+            {
+                ConvLaunch c = conv_desc(base, L.up_c1[0], prec, B, ro, ro, 3, S3D_ACT_NONE);
+                c.scale = c.shift = nullptr;
+                c.nsrc = 1;
+                c.src[0] = plain_src(ws + W.up1_u, Ct);
+                c.pre = ws + W.pre; c.pre_bdiv = 1;
+                c.out = ws + W.up1_pre;
+                TRY(launch_conv(c, st));
+            }
+            TRY(launch_slice_table_act(ws + W.up1_pre, base + L.up1_tab, base + L.up_c1[0].scale, base + L.up_c1[0].shift,
+                                       ws + W.mid, B, ns, ro, Ct, st));
+        } else {
+            {  // ConvTranspose2d 2x2 s2 as a 1x1 GEMM with N = 4*Ct and a quadrant-scatter store
+                ConvLaunch c = conv_desc(base, L.up_t[i], prec, B * ns, rp, rp, 1, S3D_ACT_NONE);
+                c.nsrc = 1;
+                c.src[0] = plain_src(prev, C);
+                c.out = ws + W.up;
+                c.out_mode = S3D_OUT_CONVT;
+                c.cout_store = Ct;
+                TRY(launch_conv(c, st));
+            }
+            {  // the up half of conv0: its accumulators start at the skip half's products, K = 9 Ct per slice instead of 18 Ct
+                ConvLaunch c = conv_desc(base, L.up_c1[i], prec, B * ns, ro, ro, 3, S3D_ACT_RELU);
+                c.nsrc = 1;
+                c.src[0] = plain_src(ws + W.up, Ct);
+                c.pre = ws + W.pre; c.pre_bdiv = ns;
+                c.out = ws + W.mid;
+                TRY(launch_conv(c, st));
+            }
         }
         {
             ConvLaunch c = conv_desc(base, L.up_c2[i], prec, B * ns, ro, ro, 3, S3D_ACT_RELU);

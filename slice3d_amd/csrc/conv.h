@@ -61,6 +61,11 @@ struct ConvLaunch {
     size_t splitk_floats;
     DropCfg drop;        // NHWC mode only: v *= dropout mask (index = output element index), before the residual
     ConvGn gn;           // LDS-staged 3x3 kernel only (launch_conv refuses it elsewhere): GroupNorm of the input, see ConvGn
+    const float* pre;    // optional pre-activation addend, NHWC [n_pre][H][W][CoutPad]:  y = act((acc + pre[img(n)][y][x][co]) * scale + shift),
+    int pre_bdiv, pre_bmod;  // img(n) = (pre_bmod ? n % pre_bmod : n) / pre_bdiv (ConvSrc's rule).  The accumulators START at it, so a
+                         // term of the sum that many images share (a K segment whose source has bdiv > 1) is computed once per
+                         // source image by a raw launch (no scale / shift / act) and added here.  3x3 stride-1 launches without a
+                         // split-K workspace only; launch_conv refuses it elsewhere
     int* splits_out;     // HOST pointer, optional.  Non-NULL: a split-K launch leaves its raw partial sums in splitk_ws
                          // ([split][pixel][CoutPad]) and skips the finish pass — *splits_out = number of splits (1: `out` is
                          // final) — for a consumer that sums them itself (the GroupNorm statistics kernels, ldm_ops.hip)
@@ -125,6 +130,14 @@ int launch_bn_relu_pool(const float* in, const float* scale, const float* shift,
                         int w, int c, hipStream_t stream);
 int launch_nchw_to_nhwc(const float* in, float* out, int n, int c, int h, int w, int cpad, hipStream_t stream);
 int launch_nhwc_to_nchw(const float* in, float* out, int n, int c, int h, int w, hipStream_t stream);
+// The U-Net decoder's slice-invariant terms (api.hip, s3d_unet_encode_fwd): image (b, s) of a (B * ns)-image NHWC tensor from a
+// per-image tensor and a per-slice term that depends on the weights only.  C % 4 == 0.
+//   bcast_add:  out[b*ns + s][p][c] = a[b][p][c] + v[s][c]                                       (p < npix)
+//   table_act:  out[b*ns + s][y][x][c] = relu((a[b][y][x][c] + tab[s][cls(y)][cls(x)][c]) * scale[c] + shift[c])   (R x R maps)
+//               cls(i) = 0 for i == 0, 3 for i == R - 1, else 1 for odd i and 2 for even i  (tab: [ns][4][4][C])
+int launch_slice_bcast_add(const float* a, const float* v, float* out, int B, int ns, long npix, int C, hipStream_t stream);
+int launch_slice_table_act(const float* a, const float* tab, const float* scale, const float* shift, float* out, int B, int ns,
+                           int R, int C, hipStream_t stream);
 int launch_add_nchw(const float* a, const float* b, float* out, int n, int c, int h, int w, hipStream_t stream);   // out NHWC = a NHWC + b NCHW
 
 // VGG-loss helpers (conv.hip)

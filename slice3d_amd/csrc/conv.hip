@@ -131,6 +131,15 @@ __device__ __forceinline__ void conv_epilogue(const ConvLaunch& a, f32x4 (&acc)[
     }
 }
 
+// Starting value of the accumulators of pixel (n, y, x), channels co .. co + 3: zero, or the launch's pre-activation addend
+// (ConvLaunch::pre).  PRE is a template flag of the kernels that serve it: a launch without an addend runs the code it ran before.
+template <bool PRE>
+__device__ __forceinline__ f32x4 conv_acc_init(const ConvLaunch& a, bool valid, int n, int y, int x, int co) {
+    if (!PRE || !valid) return zero4();
+    const int ni = (a.pre_bmod ? n % a.pre_bmod : n) / a.pre_bdiv;
+    return ld4(a.pre + ((long)(ni * a.H + y) * a.W + x) * a.CoutPad + co);
+}
+
 // Workgroups are dealt to the 8 XCDs round-robin by linear block id.  The cout tiles of one pixel tile read the same
 // input: mapped to consecutive block ids they land on different XCDs and every L2 fetches that input again (up to
 // CoutPad / CO_WG times).  Remapped, XCD x owns the pixel tiles x, x+8, ... and runs all cout tiles of a pixel tile
@@ -154,7 +163,7 @@ __device__ __forceinline__ void conv_block_tile(const ConvLaunch& a, int n_co_bl
     }
 }
 
-template <int MT, int NT, int WM, int WN, int KS>
+template <int MT, int NT, int WM, int WN, int KS, bool PRE = false>
 __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(const ConvLaunch a) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -185,13 +194,13 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(const ConvLaunc
         px[mt] = r - py[mt] * a.W;
     }
 
+    const int jt0 = blk_co * (CO_WG / 16) + wn * NT;
     f32x4 acc[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = zero4();
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = conv_acc_init<PRE>(a, pv[mt], pn[mt], py[mt], px[mt], (jt0 + nt) * 16 + 4 * g);
 
-    const int jt0 = blk_co * (CO_WG / 16) + wn * NT;
     int ubase = 0;
 #pragma unroll 1
     for (int s = 0; s < a.nsrc; ++s) {
@@ -240,7 +249,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(const ConvLaunc
 // split-precision variant: same tiling, 32-deep K chunks, A = pre-packed f16 hi/lo fragment pairs,
 // B = fp32 activations split into hi/lo on the fly, 3 f16 MFMAs per product (see decode_f16.hip).
 // ---------------------------------------------------------------------------------------------
-template <int MT, int NT, int WM, int WN, int KS>
+template <int MT, int NT, int WM, int WN, int KS, bool PRE = false>
 __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_f16x3_kernel(const ConvLaunch a) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -272,13 +281,13 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_f16x3_kernel(const Con
         py[mt] = r / a.W;
         px[mt] = r - py[mt] * a.W;
     }
+    const int jt0 = blk_co * (CO_WG / 16) + wn * NT;
     f32x4 acc[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = zero4();
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = conv_acc_init<PRE>(a, pv[mt], pn[mt], py[mt], px[mt], (jt0 + nt) * 16 + 4 * g);
 
-    const int jt0 = blk_co * (CO_WG / 16) + wn * NT;
     int ubase = 0;
 #pragma unroll 1
     for (int s = 0; s < a.nsrc; ++s) {
@@ -788,8 +797,11 @@ extern "C" void s3d_debug_c3_stamps(unsigned long long* out) {
 #else
 #define C3_STAMP(i)
 #endif
-template <int MT, int WP, int WC, int NBUF, bool GN = false>
-__global__ __launch_bounds__(256) void conv3x3_lds_f16x3_kernel(const ConvLaunch a, int tiles_x, int tiles_y,
+// PRE (ConvLaunch::pre): the 32-channel tile is held to the three waves per SIMD of its plain form (left to itself the compiler
+// spends 5 registers more and loses the third).  Only its two-buffer form is built: under that bound the one-buffer form spills,
+// and with three workgroups per CU either way the second buffer costs no occupancy.
+template <int MT, int WP, int WC, int NBUF, bool GN = false, bool PRE = false>
+__global__ __launch_bounds__(256, (PRE && MT == 2) ? 3 : 1) void conv3x3_lds_f16x3_kernel(const ConvLaunch a, int tiles_x, int tiles_y,
                                                                 int chunks_per_split) {
     static_assert(MT * WP == 8 && WP * WC == 4, "tile is 8 rows, 4 waves");
     constexpr int NT = 2, CO_WG = WC * NT * 16;
@@ -894,6 +906,15 @@ __global__ __launch_bounds__(256) void conv3x3_lds_f16x3_kernel(const ConvLaunch
     C3_STAMP(0);   // first fetch issued, table in LDS
     park(ch_lo & (NBUF - 1));
     C3_STAMP(1);   // first halo arrived and parked
+    if (PRE) {   // the accumulators start at the addend: requested once the first halo is parked (its staging registers are free: requested
+                 // with the halo in flight the loads cost the 32-channel tile a wave per SIMD), needed at the first MFMA
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const int y = y0 + MT * wp + mt, x = x0 + m;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = conv_acc_init<true>(a, y < a.H && x < a.W, n, y, x, (jt0 + nt) * 16 + 4 * g);
+        }
+    }
     __syncthreads();
     C3_STAMP(2);   // barrier
 #pragma unroll 1
@@ -1322,6 +1343,11 @@ static int launch_conv3x3_lds(const ConvLaunch& a, hipStream_t stream) {
             hipLaunchKernelGGL((conv3x3_lds_f16x3_kernel<4, 2, 2, 2, true>), grid, dim3(256), 0, stream, a, tiles_x, tiles_y, cps);
         else
             hipLaunchKernelGGL((conv3x3_lds_f16x3_kernel<2, 4, 1, 2, true>), grid, dim3(256), 0, stream, a, tiles_x, tiles_y, cps);
+    } else if (a.pre) {   // (launch_conv: no split-K workspace with an addend, so splits == 1)
+        if (co_wg == 64)
+            hipLaunchKernelGGL((conv3x3_lds_f16x3_kernel<4, 2, 2, 2, false, true>), grid, dim3(256), 0, stream, a, tiles_x, tiles_y, cps);
+        else
+            hipLaunchKernelGGL((conv3x3_lds_f16x3_kernel<2, 4, 1, 2, false, true>), grid, dim3(256), 0, stream, a, tiles_x, tiles_y, cps);
     } else if (co_wg == 64) {
         hipLaunchKernelGGL((conv3x3_lds_f16x3_kernel<4, 2, 2, 2>), grid, dim3(256), 0, stream, a, tiles_x, tiles_y, cps);
     } else {
@@ -1346,6 +1372,12 @@ static int launch_cfg(const ConvLaunch& a, hipStream_t stream) {
     dim3 grid((unsigned)nblk), block(WM * WN * 64);
     bool f16 = a.wpk16 != nullptr && (a.KU % 2 == 0);
     for (int s = 0; s < a.nsrc; ++s) f16 = f16 && (a.src[s].C % 32 == 0);
+    if (a.pre) {   // (launch_conv: 3x3 only)
+        if (f16) hipLaunchKernelGGL((conv_igemm_f16x3_kernel<MT, NT, WM, WN, 3, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((conv_igemm_kernel<MT, NT, WM, WN, 3, true>), grid, block, 0, stream, a);
+        S3D_LAUNCH_CHECK();
+        return 0;
+    }
     if (f16) {
         if (a.ks == 3)
             hipLaunchKernelGGL((conv_igemm_f16x3_kernel<MT, NT, WM, WN, 3>), grid, block, 0, stream, a);
@@ -1380,6 +1412,14 @@ int launch_conv(const ConvLaunch& a_in, hipStream_t stream) {
     // every tile shape of the menu below — and would index dropout / gate / residual by the SCATTERED offset.
     S3D_CHECK_ARG(a.out_mode != S3D_OUT_CONVT || (a.drop.p <= 0.f && !a.gate && !a.residual && !a.out_accumulate),
                   "conv: ConvTranspose output takes no dropout / gate / residual / accumulate");
+    // A pre-activation addend is the accumulators' starting value in the 3x3 kernels.  Not served: the ConvTranspose scatter,
+    // split-K (every split would start at it; the small-map kernels run on split-K only), the 1x1 row-linear kernels, a fused
+    // GroupNorm instantiation
+    S3D_CHECK_ARG(!a.pre || (a.ks == 3 && a.stride <= 1 && !a.Hin && !a.Win), "conv: a pre-activation addend is served for 3x3 stride-1 convolutions only");
+    S3D_CHECK_ARG(!a.pre || a.out_mode != S3D_OUT_CONVT, "conv: a pre-activation addend with a ConvTranspose output");
+    S3D_CHECK_ARG(!a.pre || !a.splitk_ws, "conv: a pre-activation addend with a split-K workspace");
+    S3D_CHECK_ARG(!a.pre || !a.gn.table, "conv: a pre-activation addend with a fused GroupNorm");
+    S3D_CHECK_ARG(!a.pre || (a.pre_bdiv >= 1 && a.pre_bmod >= 0), "conv: addend image rule bdiv %d bmod %d", a.pre_bdiv, a.pre_bmod);
     if (conv3x3_lds_eligible(a)) return launch_conv3x3_lds(a, stream);
     S3D_CHECK_ARG(!a.gn.table, "conv: a fused GroupNorm needs the LDS-staged 3x3 kernel (ks 3, stride 1, channel counts multiples of 32)");
     if (conv1x1_small_eligible(a)) {
@@ -1642,6 +1682,59 @@ int launch_nchw_to_nhwc(const float* in, float* out, int n, int c, int h, int w,
 
 // out (N,H,W,C) = a (N,H,W,C) + b (N,C,H,W): the c_fmaps injection of the gen_slices U-Net (openaimodel.py:735-746) without the
 // NHWC copy of the feature map in between (the same additions as nchw_to_nhwc + add: bit-identical, one launch less)
+// the two elementwise kernels of the U-Net decoder's slice-invariant terms (conv.h)
+__global__ __launch_bounds__(256) void slice_bcast_add_kernel(const float* __restrict__ a, const float* __restrict__ v,
+                                                              float* __restrict__ out, int ns, long npix, int C, long total) {
+    const int cq = C >> 2;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(idx % cq) * 4;
+        const long ip = idx / cq, img = ip / npix, p = ip - img * npix;
+        const long b = img / ns;
+        const int s = (int)(img - b * ns);
+        const f32x4 r = ld4(a + (b * npix + p) * C + c) + ld4(v + (long)s * C + c);
+        __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(out + idx * 4));
+    }
+}
+int launch_slice_bcast_add(const float* a, const float* v, float* out, int B, int ns, long npix, int C, hipStream_t stream) {
+    S3D_CHECK_ARG(a && v && out && B >= 1 && ns >= 1 && npix >= 1 && C >= 4 && C % 4 == 0, "slice_bcast_add: bad argument");
+    const long total = (long)B * ns * npix * (C >> 2);
+    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(slice_bcast_add_kernel, dim3(blocks), dim3(256), 0, stream, a, v, out, ns, npix, C, total);
+    S3D_LAUNCH_CHECK();
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void slice_table_act_kernel(const float* __restrict__ a, const float* __restrict__ tab,
+                                                              const float* __restrict__ scale, const float* __restrict__ shift,
+                                                              float* __restrict__ out, int ns, int R, int C, long total) {
+    const int cq = C >> 2;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(idx % cq) * 4;
+        long ip = idx / cq;
+        const int x = (int)(ip % R);
+        ip /= R;
+        const int y = (int)(ip % R);
+        const long img = ip / R, b = img / ns;
+        const int s = (int)(img - b * ns);
+        const int cy = y == 0 ? 0 : y == R - 1 ? 3 : (y & 1) ? 1 : 2, cx = x == 0 ? 0 : x == R - 1 ? 3 : (x & 1) ? 1 : 2;
+        f32x4 r = ld4(a + ((b * R + y) * R + x) * C + c) + ld4(tab + (long)((s * 4 + cy) * 4 + cx) * C + c);
+        r = r * ld4(scale + c) + ld4(shift + c);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = fmaxf(r[i], 0.f);
+        __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(out + idx * 4));
+    }
+}
+int launch_slice_table_act(const float* a, const float* tab, const float* scale, const float* shift, float* out, int B, int ns,
+                           int R, int C, hipStream_t stream) {
+    S3D_CHECK_ARG(a && tab && scale && shift && out && B >= 1 && ns >= 1 && R >= 2 && C >= 4 && C % 4 == 0,
+                  "slice_table_act: bad argument");
+    const long total = (long)B * ns * R * R * (C >> 2);
+    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(slice_table_act_kernel, dim3(blocks), dim3(256), 0, stream, a, tab, scale, shift, out, ns, R, C, total);
+    S3D_LAUNCH_CHECK();
+    return 0;
+}
+
 __global__ void add_nchw_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int n, int c,
                                 int h, int w) {
     const long total = (long)n * h * w * c;

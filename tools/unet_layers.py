@@ -3,7 +3,8 @@ tools/unet_layers_run.py, against the per-layer FLOP table of BASELINE.md sectio
 
     rocprofv3 --kernel-trace -d /tmp/ul -o u -- python tools/unet_layers_run.py ; python tools/unet_layers.py <db> [B]
 The encode launches its layers in a fixed order (api.hip: 13 encoder convs with BN+ReLU+pool after the taps, trans_c,
-then trans_up / ConvT / 3x3 / 3x3 per up stage); a split-K layer adds a conv_splitk_finish_kernel right after its conv."""
+the latent's broadcast add, then trans_up / skip-half 3x3 (both once per image) / ConvT / up-half 3x3 / 3x3 per up stage, up1 with its
+table kernel after the up-half 3x3); a split-K layer adds a conv_splitk_finish_kernel right after its conv."""
 import sqlite3
 import sys
 
@@ -13,18 +14,29 @@ ENC = [("conv1_1 3->64 @256", 0.23), ("conv1_2 64->64 @256", 4.83), ("conv2_1 64
        ("conv4_3 512->512 @32", 4.83), ("conv5_1 512->512 @16", 1.21), ("conv5_2 512->512 @16", 1.21),
        ("conv5_3 512->512 @16", 1.21)]
 TAPS = {1, 3, 6, 9}
+# The decoder computes what does not depend on the slice once per image (api.hip, s3d_unet_encode_fwd): the skip 1x1 and the
+# skip half of every first 3x3 (the reference runs both on the 12x expanded batch: 3.22 and 28.99 / 2 GFLOP), trans_c over
+# the 512 image channels, and the whole of up1 in front of its first BatchNorm; the per-slice parts of the latter two come from
+# the packed image through two elementwise kernels (0 FLOP here)
 UP = []
 for i, (c, r) in enumerate(((512, 32), (256, 64), (128, 128), (64, 256))):
-    # skip 1x1 runs once per image here (the reference runs it on the 12x expanded batch: 3.22 GFLOP)
-    UP += [("up%d skip 1x1 %d->%d @%d (per image)" % (i + 1, c, c // 2, r), 3.22 / 12), ("up%d ConvT %d->%d" % (i + 1, c, c // 2), 3.22),
-           ("up%d 3x3 %d->%d @%d" % (i + 1, c, c // 2, r), 28.99), ("up%d 3x3 %d->%d @%d" % (i + 1, c // 2, c // 2, r), 14.50)]
-LAYERS = ENC + [("trans_c 1x1 (512 per image + slice bias) @16", 2.01 * 512 / 640)] + UP
+    one = i == 0
+    UP += [("up%d skip 1x1 %d->%d @%d (per image)" % (i + 1, c, c // 2, r), 3.22 / 12),
+           ("up%d skip-half 3x3 %d->%d @%d (per image)" % (i + 1, c // 2, c // 2, r), 28.99 / 2 / 12),
+           ("up%d ConvT %d->%d%s" % (i + 1, c, c // 2, " (per image)" if one else ""), 3.22 / (12 if one else 1)),
+           ("up%d up-half 3x3 %d->%d @%d + per-image term%s" % (i + 1, c // 2, c // 2, r, " (per image)" if one else ""),
+            28.99 / 2 / (12 if one else 1))]
+    if one:
+        UP += [("up1 + slice table, BN, ReLU -> 12 slices", 0.0)]
+    UP += [("up%d 3x3 %d->%d @%d" % (i + 1, c // 2, c // 2, r), 14.50)]
+LAYERS = ENC + [("trans_c 1x1 512->512 @16 (per image)", 2.01 * 512 / 640 / 12), ("latent = per image + slice vector -> 12 slices", 0.0)] + UP
 
 
 def main(path, batch):
     db = sqlite3.connect(path)
     rows = db.execute("select name, start, end from kernels order by start").fetchall()
-    conv_like = lambda n: ("conv3x3_lds" in n or "conv_igemm" in n or "lin_rows" in n or "conv3x3_first" in n)
+    conv_like = lambda n: ("conv3x3_lds" in n or "conv_igemm" in n or "lin_rows" in n or "conv3x3_first" in n or "slice_bcast_add" in n
+                           or "slice_table_act" in n)
     encodes, cur = [], None
     for name, st, en in rows:
         if "conv3x3_first_kernel" in name:     # the encode's first launch
