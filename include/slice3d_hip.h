@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define S3D_VERSION 120          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding; 119: s3d_mesh_render_*; 120: s3d_unet_encode_fwd computes the decoder's slice-invariant terms once per image, the weights-only ones in s3d_unet_pack (other packed-image and workspace sizes: query them) */
+#define S3D_VERSION 121          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding; 119: s3d_mesh_render_*; 120: s3d_unet_encode_fwd computes the decoder's slice-invariant terms once per image, the weights-only ones in s3d_unet_pack (other packed-image and workspace sizes: query them); 121: up2-up4 run ConvTranspose and the first 3x3's up half as one convolution of the low-resolution map with weights composed in s3d_unet_pack (packed-image and workspace sizes change again) */
 #define S3D_E_ARG (-1)           /* bad argument / unsupported shape */
 #define S3D_E_WORKSPACE (-2)     /* workspace or packed-weight buffer too small */
 
@@ -85,7 +85,9 @@ typedef struct {
     int n_slices;
 } S3dUNetParams;
 
-/* Bytes of the packed (MFMA-fragment-ordered, BN-folded) weight image for n_slices. */
+/* Bytes of the packed (MFMA-fragment-ordered, BN-folded) weight image for n_slices.  The image also keeps the pack's
+ * own intermediates (the ConvT output behind up1's slice table, the fp32 composed ConvT -> 3x3 operators of up2 .. up4, about
+ * 2.6 MB): a queued pack may read them after s3d_unet_pack returns, so they are not shared between stages. */
 size_t s3d_unet_packed_bytes(int n_slices);
 /* Repack raw parameters into `packed` (device, >= s3d_unet_packed_bytes).  Re-run after every
  * parameter update.  `params_host` is a HOST struct of DEVICE pointers. */

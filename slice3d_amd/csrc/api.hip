@@ -162,6 +162,11 @@ struct UNetLayout {
     size_t up1_tab;     // [ns][4][4][256]: up1's first 3x3 (up half) over ConvT(a map of v[s]) + bias, raw: one value per
                         // (first | odd | even | last) row and column class — the per-slice part of up1's first pre-activation
     size_t up1_tab_in;  // [ns][4][4][256]: that ConvT output (scratch of the pack)
+    // up2 .. up4 (index 1 .. 3): ConvTranspose and the first 3x3's up half run as ONE 2x2-per-parity convolution of the low-resolution
+    // map (ConvLaunch::up2x; up1 has no per-slice matrix work there to begin with).  The ConvT -> 3x3 operator, rows (2 py + px) * Ct + co, K = 4 taps x C (weights only; the BN
+    // is up_c1's), its border-class bias table [3][3][Ct], and the fp32 operator as composed ([4 Ct][C][2][2]: what the pack reads)
+    PackedConv up_cc[4];
+    size_t up_tb[4], up_cc_raw[4];
     PackedConv up_c1s[4];   // the skip half of up_c1's input channels as an image of its own (weights only); up_c1 holds the up half and the BN
     size_t emds;
     size_t enc0_raw;   // conv1_1's weight as is, (64,3,3,3): the 3-channel first layer runs a direct fp32 kernel on the NCHW image
@@ -218,9 +223,22 @@ static UNetLayout unet_layout(int n_slices) {
     for (int i = 0; i < 4; ++i) {
         const int C = kUpC[i], Ct = C / 2;
         a.conv(L.trans_up[i], Ct, C / 16);
-        a.conv(L.up_t[i], 4 * Ct, C / 16);
         a.weights(L.up_c1s[i], Ct, 9 * Ct / 16);
-        a.conv(L.up_c1[i], Ct, 9 * Ct / 16);
+        if (i > 0) {   // composed: no ConvT image, no up-half image: up_c1 keeps the BatchNorm
+            L.up_t[i] = PackedConv{};
+            L.up_c1[i] = PackedConv{};
+            L.up_c1[i].cout_pad = Ct;
+            L.up_c1[i].scale = a.take(Ct);
+            L.up_c1[i].shift = a.take(Ct);
+            a.weights(L.up_cc[i], 4 * Ct, 4 * C / 16);
+            L.up_tb[i] = a.take((size_t)9 * Ct);
+            L.up_cc_raw[i] = a.take((size_t)16 * Ct * C);
+        } else {
+            a.conv(L.up_t[i], 4 * Ct, C / 16);
+            a.conv(L.up_c1[i], Ct, 9 * Ct / 16);
+            L.up_cc[i] = PackedConv{};
+            L.up_tb[i] = L.up_cc_raw[i] = 0;
+        }
         a.conv(L.up_c2[i], Ct, 9 * Ct / 16);
     }
     a.conv(L.outc, 16, 32 / 16);
@@ -302,7 +320,13 @@ extern "C" int s3d_unet_pack(const S3dUNetParams* P, void* packed, size_t packed
         TRY(pack_linear(P->trans_up[i].w, base + L.trans_up[i].w16, Ct, Ct, C, C, 0, st, 1));
         TRY(launch_fold_bn(P->trans_up[i].b, nullptr, base + L.trans_up[i].scale, base + L.trans_up[i].shift, Ct,
                            Ct, 1, 0, st));
-        {  // ConvTranspose2d weight [Cin][Ct][2][2] -> GEMM rows n = q*Ct + co
+        if (i > 0) {
+            // Wc and Tb from the raw weights (float64 sums, one fp32 rounding), then the fragment images in the K order the kernel
+            // walks: tap a * 2 + b, channel.  Each stage has its own raw buffer: a queued pack may read it long after this call
+            TRY(launch_upconv_compose(P->up_t[i].w, P->up_t[i].b, P->up_c1[i].w, C, Ct, C, Ct, base + L.up_cc_raw[i], base + L.up_tb[i], st));
+            TRY(pack_conv3(base + L.up_cc_raw[i], base + L.up_cc[i].w, 4 * Ct, 4 * Ct, C, 0, C, L.up_cc[i].KU, 0, 4, st));
+            TRY(pack_conv3(base + L.up_cc_raw[i], base + L.up_cc[i].w16, 4 * Ct, 4 * Ct, C, 0, C, L.up_cc[i].KU, 0, 4, st, 1));
+        } else {  // ConvTranspose2d weight [Cin][Ct][2][2] -> GEMM rows n = q*Ct + co
             PackArgs a = {};
             a.src = P->up_t[i].w; a.dst = base + L.up_t[i].w; a.kind = S3D_PACK_CONVT;
             a.n_valid = 4 * Ct; a.n_pad = 4 * Ct; a.KU_total = C / 16; a.u_off = 0; a.ku_seg = C / 16;
@@ -316,9 +340,11 @@ extern "C" int s3d_unet_pack(const S3dUNetParams* P, void* packed, size_t packed
         // DoubleConv conv0 on cat([skip_proj, up]) (unet_parts.py:73): the two halves of its input channels are two weight
         // images, because the skip half's products are the same for every slice of an image (s3d_unet_encode_fwd)
         TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1s[i].w, Ct, Ct, C, 0, Ct, L.up_c1s[i].KU, 0, 9, st));
-        TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1[i].w, Ct, Ct, C, Ct, Ct, L.up_c1[i].KU, 0, 9, st));
         TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1s[i].w16, Ct, Ct, C, 0, Ct, L.up_c1s[i].KU, 0, 9, st, 1));
-        TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1[i].w16, Ct, Ct, C, Ct, Ct, L.up_c1[i].KU, 0, 9, st, 1));
+        if (i == 0) {
+            TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1[i].w, Ct, Ct, C, Ct, Ct, L.up_c1[i].KU, 0, 9, st));
+            TRY(pack_conv3(P->up_c1[i].w, base + L.up_c1[i].w16, Ct, Ct, C, Ct, Ct, L.up_c1[i].KU, 0, 9, st, 1));
+        }
         TRY(launch_fold_bn(nullptr, P->up_c1[i].bn, base + L.up_c1[i].scale, base + L.up_c1[i].shift, Ct, Ct, 1, 0,
                            st));
         TRY(pack_conv3(P->up_c2[i].w, base + L.up_c2[i].w, Ct, Ct, Ct, 0, Ct, L.up_c2[i].KU, 0, 9, st));
@@ -340,7 +366,7 @@ extern "C" int s3d_unet_pack(const S3dUNetParams* P, void* packed, size_t packed
 
 #define S3D_SPLITK_FLOATS ((size_t)4718592)
 struct UNetWs {
-    size_t in16, a, b, x[5], p[4], proj, pre, up, mid, splitk;
+    size_t in16, a, b, x[5], p[4], proj, pre, mid, splitk;   // (no per-slice ConvT output: up2 .. up4 never materialise it)
     size_t lat, up1_u, up1_pre;   // per-image terms of the latent and of up1
     size_t total;
 };
@@ -361,7 +387,6 @@ static UNetWs unet_ws(int B, int S, int ns) {
     for (int i = 0; i < 4; ++i) W.p[i] = take((px >> (2 * (i + 1))) * xc[i]);
     W.proj = take(px * 32);                 // largest skip projection: (B,S,S,32)
     W.pre = take(px * 32);                  // its 3x3 products, the per-image term of up_c1: same shape
-    W.up = take(px * ns * 32);              // largest ConvT output: (B*ns,S,S,32)
     W.mid = take(px * ns * 32);
     W.splitk = take(S3D_SPLITK_FLOATS);   // split-K partials of the few-pixel encoder layers
     W.lat = take(px / 256 * 512);         // trans_c over the image channels: (B,S/16,S/16,512)
@@ -468,6 +493,14 @@ static int encoder_fwd(const float* base, const EncLayout& E, int prec, int N, i
     return 0;
 }
 
+// U-Net encode (unet_custom.py:40-69).  Schedule:
+//   encoder on B images; latent = trans_c(x5) per image + the pack's per-slice vector (slice_bcast_add);
+//   per up stage: skip 1x1 and the skip half of the first 3x3 once per image (raw, the per-slice launch's addend);
+//     up1:      ConvT and the up half per image, then the pack's per-slice table + BN + ReLU (slice_table_act);
+//     up2..up4: ConvT and the up half as ONE launch per stage on the low-resolution map of the B * ns slice images, with the
+//               pack's composed weights and border-class bias table (ConvLaunch::up2x) — no ConvT output in the workspace;
+//     the second 3x3 on B * ns images;
+//   OutConv 1x1 + tanh.  DESIGN.md section 4 has the algebra of every term that is computed once.
 extern "C" int s3d_unet_encode_fwd(const void* packed, const float* img, const S3dPyramid* out,
                                    float* slices_rec, int B, int S, int ns, int prec, void* workspace,
                                    size_t workspace_bytes, void* stream) {
@@ -557,23 +590,22 @@ extern "C" int s3d_unet_encode_fwd(const void* packed, const float* img, const S
             TRY(launch_slice_table_act(ws + W.up1_pre, base + L.up1_tab, base + L.up_c1[0].scale, base + L.up_c1[0].shift,
                                        ws + W.mid, B, ns, ro, Ct, st));
         } else {
-            {  // ConvTranspose2d 2x2 s2 as a 1x1 GEMM with N = 4*Ct and a quadrant-scatter store
-                ConvLaunch c = conv_desc(base, L.up_t[i], prec, B * ns, rp, rp, 1, S3D_ACT_NONE);
-                c.nsrc = 1;
-                c.src[0] = plain_src(prev, C);
-                c.out = ws + W.up;
-                c.out_mode = S3D_OUT_CONVT;
-                c.cout_store = Ct;
-                TRY(launch_conv(c, st));
-            }
-            {  // the up half of conv0: its accumulators start at the skip half's products, K = 9 Ct per slice instead of 18 Ct
-                ConvLaunch c = conv_desc(base, L.up_c1[i], prec, B * ns, ro, ro, 3, S3D_ACT_RELU);
-                c.nsrc = 1;
-                c.src[0] = plain_src(ws + W.up, Ct);
-                c.pre = ws + W.pre; c.pre_bdiv = ns;
-                c.out = ws + W.mid;
-                TRY(launch_conv(c, st));
-            }
+            // ConvT and the up half of conv0 as one launch on the low-resolution map: per output parity a 2x2 convolution with the
+            // pack's composed weights (K = 4 C instead of C + 9 Ct per pixel quad), accumulators starting at the skip half's
+            // products + the ConvT bias by border class.  The (B*ns, ro, ro, Ct) ConvT output is neither written nor read
+            ConvLaunch c = {};
+            c.wpk16 = prec != S3D_PREC_F32 ? (const void*)(base + L.up_cc[i].w16) : nullptr;
+            c.single_pass = prec == S3D_PREC_F16;
+            c.N = B * ns; c.H = rp; c.W = rp; c.ks = 2; c.up2x = 1;
+            c.CoutPad = Ct; c.wpk = base + L.up_cc[i].w; c.KU = L.up_cc[i].KU;
+            c.scale = base + L.up_c1[i].scale; c.shift = base + L.up_c1[i].shift;
+            c.act = S3D_ACT_RELU; c.out_mode = S3D_OUT_NHWC; c.cout_store = Ct; c.out_cstride = Ct;
+            c.nsrc = 1;
+            c.src[0] = plain_src(prev, C);
+            c.pre = ws + W.pre; c.pre_bdiv = ns;
+            c.pre_tab = base + L.up_tb[i];
+            c.out = ws + W.mid;
+            TRY(launch_conv(c, st));
         }
         {
             ConvLaunch c = conv_desc(base, L.up_c2[i], prec, B * ns, ro, ro, 3, S3D_ACT_RELU);

@@ -69,6 +69,16 @@ struct ConvLaunch {
     int* splits_out;     // HOST pointer, optional.  Non-NULL: a split-K launch leaves its raw partial sums in splitk_ws
                          // ([split][pixel][CoutPad]) and skips the finish pass — *splits_out = number of splits (1: `out` is
                          // final) — for a consumer that sums them itself (the GroupNorm statistics kernels, ldm_ops.hip)
+    int up2x;            // 1: ConvTranspose2d(2x2, stride 2) composed with the 3x3 that follows it.  N, H, W are
+                         // the LOW-resolution input grid, the output (and `pre`) grid is (2H, 2W) with CoutPad channels.  ks = 2: output
+                         // parity (py, px) of low-res pixel (r, c) is a 2x2 convolution over input pixels (r + py - 1 + a, c + px - 1 + b),
+                         // zero outside.  The weight image holds the four parities' rows one after the other (row = (2 py + px) * CoutPad
+                         // + co, K order tap a * 2 + b, channel), KU = 4 * C / 16.  One plain source; `pre` and `pre_tab` are required;
+                         // NHWC output with scale / shift / ReLU only.  launch_conv refuses everything else with it
+    const float* pre_tab;   // up2x: [3][3][CoutPad], added to `pre` by (row class, column class) of the output pixel — 0 first, 1 interior,
+                         // 2 last: the ConvTranspose bias seen through the in-bounds taps of the zero-padded 3x3
+    int tap_oy, tap_ox;  // up2x, set by launch_conv for the per-parity launches of the generic kernel: input pixel = output pixel + tap + origin
+    int out_py, out_px;  // ... and that launch's output parity: low-res pixel (y, x) is stored at (2 y + out_py, 2 x + out_px)
 };
 
 int launch_conv(const ConvLaunch& a, hipStream_t stream);
@@ -125,6 +135,13 @@ private:
 // rep > 1 tiles the vector (ConvT: 4 quadrants share the bias).
 int launch_fold_bn(const float* bias, const float* const bn[4], float* scale, float* shift, int c_valid,
                    int c_pad, int rep, int bias_before_bn, hipStream_t stream);
+
+// The weights-only operator of ConvTranspose2d(C -> Ct, 2x2, stride 2) followed by a 3x3 over its output (ConvLaunch::up2x):
+//   wc [(2 py + px) * Ct + co][ci][a][b] — the layout S3D_PACK_CONV reads with taps = 4 — and tb [3][3][Ct] (ConvLaunch::pre_tab).
+//   wt: the ConvT weight [C][Ct][2][2], bt: its bias [Ct]; w1: the 3x3's weight [Ct][cin_tot][3][3], of which input channels
+//   cin_begin .. cin_begin + Ct - 1 see the ConvT output.  Every element is summed in float64 and rounded to fp32 once.
+int launch_upconv_compose(const float* wt, const float* bt, const float* w1, int C, int Ct, int cin_tot, int cin_begin, float* wc,
+                          float* tb, hipStream_t stream);
 
 int launch_bn_relu_pool(const float* in, const float* scale, const float* shift, float* out, int n, int h,
                         int w, int c, hipStream_t stream);

@@ -13,6 +13,7 @@
 // MFMA per (MT|NT)-fold reuse, so the operand streams fit the L1/L2 path at this precision.
 #include <stdlib.h>
 #include "conv.h"
+#include <utility>
 #include <vector>
 
 template <int MT, int NT>
@@ -140,6 +141,20 @@ __device__ __forceinline__ f32x4 conv_acc_init(const ConvLaunch& a, bool valid, 
     return ld4(a.pre + ((long)(ni * a.H + y) * a.W + x) * a.CoutPad + co);
 }
 
+// ConvLaunch::up2x: the kernels walk the low-resolution grid; addend, table and store live on the (2H, 2W) output grid.  `e` below is
+// the launch seen from that grid, so that conv_acc_init and conv_epilogue index it as they index any NHWC output.
+__device__ __forceinline__ ConvLaunch conv_up_out_view(const ConvLaunch& a) {
+    ConvLaunch e = a;
+    e.H = 2 * a.H;
+    e.W = 2 * a.W;
+    return e;
+}
+__device__ __forceinline__ f32x4 conv_up_acc_init(const ConvLaunch& e, bool valid, int n, int y, int x, int co) {
+    if (!valid) return zero4();
+    const int cy = y == 0 ? 0 : y == e.H - 1 ? 2 : 1, cx = x == 0 ? 0 : x == e.W - 1 ? 2 : 1;
+    return conv_acc_init<true>(e, true, n, y, x, co) + ld4(e.pre_tab + (cy * 3 + cx) * e.CoutPad + co);
+}
+
 // Workgroups are dealt to the 8 XCDs round-robin by linear block id.  The cout tiles of one pixel tile read the same
 // input: mapped to consecutive block ids they land on different XCDs and every L2 fetches that input again (up to
 // CoutPad / CO_WG times).  Remapped, XCD x owns the pixel tiles x, x+8, ... and runs all cout tiles of a pixel tile
@@ -163,7 +178,9 @@ __device__ __forceinline__ void conv_block_tile(const ConvLaunch& a, int n_co_bl
     }
 }
 
-template <int MT, int NT, int WM, int WN, int KS, bool PRE = false>
+// UP (ConvLaunch::up2x, one output parity per launch: tap_oy / tap_ox, out_py / out_px): KS = 2, the pixel grid is the low-resolution
+// input grid, accumulators start at addend + table of the output pixel (2 y + out_py, 2 x + out_px), which is where the store goes
+template <int MT, int NT, int WM, int WN, int KS, bool PRE = false, bool UP = false>
 __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(const ConvLaunch a) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -199,7 +216,12 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(const ConvLaunc
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = conv_acc_init<PRE>(a, pv[mt], pn[mt], py[mt], px[mt], (jt0 + nt) * 16 + 4 * g);
+        for (int nt = 0; nt < NT; ++nt) {
+            if constexpr (UP)
+                acc[mt][nt] = conv_up_acc_init(conv_up_out_view(a), pv[mt], pn[mt], 2 * py[mt] + a.out_py, 2 * px[mt] + a.out_px, (jt0 + nt) * 16 + 4 * g);
+            else
+                acc[mt][nt] = conv_acc_init<PRE>(a, pv[mt], pn[mt], py[mt], px[mt], (jt0 + nt) * 16 + 4 * g);
+        }
 
     int ubase = 0;
 #pragma unroll 1
@@ -208,7 +230,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(const ConvLaunc
         const int cu = S.C >> 4;
 #pragma unroll 1
         for (int tap = 0; tap < KS * KS; ++tap) {
-            const int dy = tap / KS - PAD, dx = tap % KS - PAD;
+            const int dy = tap / KS - PAD + (UP ? a.tap_oy : 0), dx = tap % KS - PAD + (UP ? a.tap_ox : 0);
             const float* bp[MT];
             bool ok[MT];
 #pragma unroll
@@ -242,7 +264,16 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(const ConvLaunc
         ubase += KS * KS * cu;
     }
 
-    conv_epilogue<MT, NT>(a, acc, pn, py, px, pv, jt0, g);
+    if constexpr (UP) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            py[mt] = 2 * py[mt] + a.out_py;
+            px[mt] = 2 * px[mt] + a.out_px;
+        }
+        conv_epilogue<MT, NT>(conv_up_out_view(a), acc, pn, py, px, pv, jt0, g);
+    } else {
+        conv_epilogue<MT, NT>(a, acc, pn, py, px, pv, jt0, g);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1009,6 +1040,225 @@ __global__ __launch_bounds__(256, (PRE && MT == 2) ? 3 : 1) void conv3x3_lds_f16
     conv_epilogue<MT, NT>(a, acc, pn, py, px, pv, jt0, g);
 }
 
+// ---------------------------------------------------------------------------------------------
+// ConvTranspose2d(2x2, stride 2) composed with the 3x3 that follows it (ConvLaunch::up2x), split precision: the LDS-staged kernel
+// above on the LOW-resolution grid.  The halo tile, its hi / lo staging and the swizzle are the same; output parity (py, px) of
+// low-res pixel (r, c) reads the four taps at halo offsets (py + a, px + b), a, b in {0, 1}, and is stored at (2r + py, 2c + px).
+// A workgroup serves NPY x NPX parities of CO_WG channels from ONE staged tile: the 3 x 3 halo offsets the four parities
+// touch between them are read from LDS once each (ey, ex below) and feed every (parity, tap) pair that lands on them — 16
+// products from 9 fragment reads with all four parities, against 9 from 9 for the plain 3x3.  Per parity the products are added
+// in the order tap (a, b) ascending inside a chunk, chunks ascending, whatever the parity grouping: the bits of a parity do not
+// depend on NPY / NPX.  Accumulators start at the addend; the border-class table is added after the K loop, in the epilogue.  No split-K, no GroupNorm, one source.
+// ---------------------------------------------------------------------------------------------
+struct UpStep {
+    int ey, ex, iy, ix;   // halo offset (relative to the workgroup's first parity) and the parity of the group that uses it: tap a = ey - iy, b = ex - ix
+};
+template <int NPY, int NPX>
+__host__ __device__ constexpr UpStep up_step(int s) {
+    int k = 0;
+    for (int ey = 0; ey <= NPY; ++ey)
+        for (int ex = 0; ex <= NPX; ++ex)
+            for (int iy = 0; iy < NPY; ++iy)
+                for (int ix = 0; ix < NPX; ++ix)
+                    if (ey - iy >= 0 && ey - iy <= 1 && ex - ix >= 0 && ex - ix <= 1) {
+                        if (k == s) return UpStep{ey, ex, iy, ix};
+                        ++k;
+                    }
+    return UpStep{-1, -1, -1, -1};
+}
+template <int... S, class F>
+__device__ __forceinline__ void up_static_for(std::integer_sequence<int, S...>, F&& f) {
+    (f(std::integral_constant<int, S>{}), ...);
+}
+
+template <int MT, int WP, int WC, int NPY, int NPX, int NBUF, int OCC>
+__global__ __launch_bounds__(256, OCC) void conv_up2x_lds_f16x3_kernel(const ConvLaunch a, int tiles_x, int tiles_y) {
+    static_assert(MT * WP == 8 && WP * WC == 4, "tile is 8 rows, 4 waves");
+    static_assert((NPY == 1 || NPY == 2) && (NPX == 1 || NPX == 2), "one or both parities per direction");
+    constexpr int NT = 2, CO_WG = WC * NT * 16, NPAR = NPY * NPX, NSTEP = 4 * NPAR;
+    __shared__ __attribute__((aligned(16))) _Float16 s_in[NBUF][2][C3_HALO * C3_PXS];   // [buf][hi|lo]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int m = lane & 15, g = lane >> 4;
+    const int wp = wave % WP, wc = wave / WP;
+    const int Ct = a.CoutPad, n_cb = Ct / CO_WG;
+    const int n_co_blk = n_cb * (2 / NPY) * (2 / NPX);   // (channel block, parity group) pairs of one pixel tile
+    int blk_co;
+    long blk_tile;
+    conv_block_tile(a, n_co_blk, blk_co, blk_tile);
+    const int cb = blk_co % n_cb, pg = blk_co / n_cb;
+    const int py0 = NPY == 2 ? 0 : pg / (2 / NPX), px0 = NPX == 2 ? 0 : pg % (2 / NPX);   // first parity of the group
+    int tile = (int)blk_tile;
+    const int tx = tile % tiles_x;
+    tile /= tiles_x;
+    const int ty = tile % tiles_y, n = tile / tiles_y;
+    const int x0 = tx * 16, y0 = ty * 8;
+    const int KU32 = a.KU >> 1;
+    const ConvSrc S = a.src[0];
+    const int cu = S.C >> 5;
+    const _Float16* wimg = reinterpret_cast<const _Float16*>(a.wpk16);
+    const int jt0 = cb * (CO_WG / 16) + wc * NT;   // first 16-channel tile of this wave inside a parity's Ct channels
+    const int Ho = 2 * a.H, Wo = 2 * a.W;          // the output grid
+
+    f32x4 acc[NPAR][MT][NT];
+
+    // staging: as conv3x3_lds_f16x3_kernel (thread t handles halo slots t, t + 256, ...; slot = pixel * 8 + channel quad)
+    constexpr int NSLOT = C3_HALO * 8;
+    constexpr int NPRE = (NSLOT + 255) / 256;
+    f32x4 pre[NPRE];
+    const int ni = (S.bmod ? n % S.bmod : n) / S.bdiv;
+    auto fetch = [&](int c) {
+#pragma unroll
+        for (int i = 0; i < NPRE; ++i) {
+            const int slot = threadIdx.x + 256 * i;
+            const int pix = slot >> 3, q4 = slot & 7;
+            const int hy = pix / 18, hx = pix - hy * 18;
+            const int y = y0 + hy - 1, x = x0 + hx - 1;
+            const bool ok = slot < NSLOT && y >= 0 && y < a.H && x >= 0 && x < a.W;
+            const long off = ((long)(ni * a.H + (ok ? y : 0)) * a.W + (ok ? x : 0)) * S.C + 32 * c + 4 * q4;
+            const f32x4 v = ld4(S.p + off);           // always a valid address; masked below
+            pre[i] = ok ? v : zero4();
+        }
+    };
+    auto park = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < NPRE; ++i) {
+            const int slot = threadIdx.x + 256 * i;
+            if (slot < NSLOT) {
+                const int pix = slot >> 3, q4 = slot & 7;
+                s3d_half4 hi, lo;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const _Float16 h = (_Float16)pre[i][t];
+                    hi[t] = h;
+                    lo[t] = (_Float16)(pre[i][t] - (float)h);
+                }
+                const int po = pix * C3_PXS + C3_SWZ(pix, q4 >> 1) + 4 * (q4 & 1);
+                *reinterpret_cast<s3d_half4*>(&s_in[buf][0][po]) = hi;
+                *reinterpret_cast<s3d_half4*>(&s_in[buf][1][po]) = lo;
+            }
+        }
+    };
+    fetch(0);
+    park(0);
+    // the addend of every output pixel of this wave: requested once the first halo is parked (its staging registers are free), straight
+    // into the accumulators.  The border-class table joins after the K loop (below): with it here, 2 x 4 NPAR MT loads are in flight at once
+#pragma unroll
+    for (int par = 0; par < NPAR; ++par)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const int r = y0 + MT * wp + mt, c = x0 + m;
+            const int y = 2 * r + py0 + par / NPX, x = 2 * c + px0 + par % NPX;
+            const float* ad = a.pre + ((long)(((a.pre_bmod ? n % a.pre_bmod : n) / a.pre_bdiv) * Ho + y) * Wo + x) * Ct + 4 * g;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[par][mt][nt] = r < a.H && c < a.W ? ld4(ad + (jt0 + nt) * 16) : zero4();
+        }
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+#pragma unroll 1
+    for (int ch = 0; ch < cu; ++ch) {
+        // fragment (parity, tap, nt) of this chunk: row tile (2 py + px) * Ct / 16 + jt0 + nt, K chunk tap * cu + ch
+        const _Float16* wp0 = wimg + ((size_t)jt0 * KU32 + ch) * 1024 + lane * 8;
+        auto wfrag = [&](const UpStep st, int nt) {
+            const int par = (py0 + st.iy) * 2 + px0 + st.ix, tap = (st.ey - st.iy) * 2 + st.ex - st.ix;
+            return wp0 + ((size_t)(par * (Ct >> 4) + nt) * KU32 + (size_t)tap * cu) * 1024;
+        };
+        // weight fragments of the first step are requested BEFORE the halo prefetch (vmcnt retires in order)
+        s3d_half8 wh[NT], wl[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const _Float16* f = wfrag(up_step<NPY, NPX>(0), nt);
+            wh[nt] = *reinterpret_cast<const s3d_half8*>(f);
+            wl[nt] = *reinterpret_cast<const s3d_half8*>(f + 512);
+        }
+        if (ch + 1 < cu) fetch(ch + 1);
+        const _Float16* sh = s_in[ch & (NBUF - 1)][0];
+        const _Float16* sl = s_in[ch & (NBUF - 1)][1];
+        s3d_half8 bh[MT], bl[MT];
+        up_static_for(std::make_integer_sequence<int, NSTEP>{}, [&](auto sc) {
+            constexpr int s = decltype(sc)::value;
+            constexpr UpStep st = up_step<NPY, NPX>(s);
+            s3d_half8 nwh[NT], nwl[NT];
+            if constexpr (s + 1 < NSTEP) {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const _Float16* f = wfrag(up_step<NPY, NPX>(s + 1), nt);
+                    nwh[nt] = *reinterpret_cast<const s3d_half8*>(f);
+                    nwl[nt] = *reinterpret_cast<const s3d_half8*>(f + 512);
+                }
+            }
+            constexpr UpStep prev = up_step<NPY, NPX>(s > 0 ? s - 1 : 0);
+            if constexpr (s == 0 || prev.ey != st.ey || prev.ex != st.ex) {   // a new halo offset: output (r, m) reads halo (r + py0 + ey, m + px0 + ex)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const int pix = (MT * wp + mt + py0 + st.ey) * 18 + m + px0 + st.ex;
+                    const int po = pix * C3_PXS + C3_SWZ(pix, g);
+                    bh[mt] = *reinterpret_cast<const s3d_half8*>(sh + po);
+                    bl[mt] = *reinterpret_cast<const s3d_half8*>(sl + po);
+                }
+            }
+            constexpr int par = st.iy * NPX + st.ix;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                if (!a.single_pass) {
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+                        acc[par][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[nt], bl[mt], acc[par][mt][nt], 0, 0, 0);
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+                        acc[par][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[nt], bh[mt], acc[par][mt][nt], 0, 0, 0);
+                }
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+                    acc[par][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[nt], bh[mt], acc[par][mt][nt], 0, 0, 0);
+            }
+            if constexpr (s + 1 < NSTEP) {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    wh[nt] = nwh[nt];
+                    wl[nt] = nwl[nt];
+                }
+            }
+            // a step's weight requests and MFMAs stay in the step (LDS reads and address arithmetic may move up): left to itself
+            // the scheduler hoists the fragment loads of all 4 NPAR steps and spills
+            __builtin_amdgcn_sched_barrier(0x2 | 0x4 | 0x100);
+        });
+        if (NBUF == 1) __syncthreads();   // everyone is done reading the single buffer before it is refilled
+        if (ch + 1 < cu) park((ch + 1) & (NBUF - 1));
+        __syncthreads();
+    }
+    // Epilogue: conv_epilogue's full-line form restricted to what this mode takes (table, scale / shift, ReLU).  After the exchange
+    // (s3d_full_line_pair) the lane owns channels co .. co + 3 of tile pixels (row, m & 7) and (row, (m & 7) + 8); a tile pixel's
+    // output position follows from its tile coordinates, so no offset travels with the exchange.  One copy of the general epilogue per
+    // parity was 90 KB of code.
+    const int co = jt0 * 16 + 16 * (m >> 3) + 4 * g;
+    const f32x4 sc = a.scale ? ld4(a.scale + co) : f32x4{1.f, 1.f, 1.f, 1.f};
+    const f32x4 sf = a.shift ? ld4(a.shift + co) : zero4();
+#pragma unroll
+    for (int par = 0; par < NPAR; ++par) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const int r = y0 + MT * wp + mt, y = 2 * r + py0 + par / NPX;
+            const int cy = y == 0 ? 0 : y == Ho - 1 ? 2 : 1;
+            f32x4 val[2];
+            s3d_full_line_pair(acc[par][mt][0], acc[par][mt][1], m, val[0], val[1]);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int c = x0 + (m & 7) + 8 * k, x = 2 * c + px0 + par % NPX;
+                if (r >= a.H || c >= a.W) continue;
+                const int cx = x == 0 ? 0 : x == Wo - 1 ? 2 : 1;
+                f32x4 v = (val[k] + ld4(a.pre_tab + (cy * 3 + cx) * Ct + co)) * sc + sf;
+                if (a.act == S3D_ACT_RELU) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], 0.f);
+                }
+                // streaming store, as conv_epilogue
+                __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(a.out + ((long)(n * Ho + y) * Wo + x) * a.out_cstride + co));
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);   // one parity at a time
+    }
+}
+
 // sums the split-K partials of 4 consecutive output channels of one pixel and applies the conv epilogue
 __global__ void conv_splitk_finish_kernel(const ConvLaunch a, int nsplit) {
     const long P = (long)a.N * a.H * a.W;
@@ -1363,6 +1613,44 @@ static int launch_conv3x3_lds(const ConvLaunch& a, hipStream_t stream) {
     return 0;
 }
 
+// ConvLaunch::up2x.  Split precision (and single pass): conv_up2x_lds_f16x3_kernel, one launch.  fp32: the generic kernel, one
+// launch per output parity on that parity's rows of the weight image (correct, not tuned: no caller times it).
+static int launch_conv_up2x(const ConvLaunch& a, hipStream_t stream) {
+    if (!a.wpk16) {
+        const long P = (long)a.N * a.H * a.W;
+        const long nblk = ((P + 31) / 32) * (a.CoutPad / 32);
+        S3D_CHECK_ARG(nblk > 0 && nblk < (1L << 31), "conv grid out of range (%ld)", nblk);
+        for (int par = 0; par < 4; ++par) {
+            ConvLaunch b = a;
+            b.wpk = a.wpk + (size_t)par * (a.CoutPad / 16) * a.KU * 256;
+            b.out_py = par >> 1; b.out_px = par & 1;
+            b.tap_oy = b.out_py - 1; b.tap_ox = b.out_px - 1;
+            hipLaunchKernelGGL((conv_igemm_kernel<1, 1, 2, 2, 2, true, true>), dim3((unsigned)nblk), dim3(256), 0, stream, b);
+            S3D_LAUNCH_CHECK();
+        }
+        return 0;
+    }
+    const int tiles_x = (a.W + 15) / 16, tiles_y = (a.H + 7) / 8;
+    const long tiles = (long)tiles_x * tiles_y * a.N;
+#define UP_LAUNCH(MT_, WP_, WC_, NPY_, NPX_, NBUF_, OCC_)                                                                        \
+    do {                                                                                                                         \
+        const long nblk = tiles * (a.CoutPad / (WC_ * 32)) * (4 / (NPY_ * NPX_));                                                  \
+        S3D_CHECK_ARG(nblk < (1L << 31), "conv grid out of range (%ld)", nblk);                                                  \
+        hipLaunchKernelGGL((conv_up2x_lds_f16x3_kernel<MT_, WP_, WC_, NPY_, NPX_, NBUF_, OCC_>), dim3((unsigned)nblk), dim3(256), 0, \
+                           stream, a, tiles_x, tiles_y);                                                                         \
+    } while (0)
+    // One staged tile serves several parities (profiles/unet_upconv_composite.md): all four on the 32-channel tile (up4: 128 virtual
+    // output channels per workgroup; one LDS buffer, K is two chunks), the two of an output row on the 64-channel tile (up3: all of
+    // its 64 channels; up2: measured 152 us against 190 us with one parity per workgroup).  Both run two waves per SIMD without
+    // scratch.  The 32-channel tile fits the three waves of the plain 3x3 with ONE parity per workgroup only; that form measured
+    // 339-340 us at up4 against 275 us for this one (the two parities of a row: 318 us).
+    if (a.CoutPad % 64 == 0) UP_LAUNCH(4, 2, 2, 1, 2, 2, 2);
+    else UP_LAUNCH(2, 4, 1, 2, 2, 1, 2);
+#undef UP_LAUNCH
+    S3D_LAUNCH_CHECK();
+    return 0;
+}
+
 template <int MT, int NT, int WM, int WN>
 static int launch_cfg(const ConvLaunch& a, hipStream_t stream) {
     constexpr int PIX_WG = WM * MT * 16, CO_WG = WN * NT * 16;
@@ -1415,11 +1703,28 @@ int launch_conv(const ConvLaunch& a_in, hipStream_t stream) {
     // A pre-activation addend is the accumulators' starting value in the 3x3 kernels.  Not served: the ConvTranspose scatter,
     // split-K (every split would start at it; the small-map kernels run on split-K only), the 1x1 row-linear kernels, a fused
     // GroupNorm instantiation
-    S3D_CHECK_ARG(!a.pre || (a.ks == 3 && a.stride <= 1 && !a.Hin && !a.Win), "conv: a pre-activation addend is served for 3x3 stride-1 convolutions only");
+    S3D_CHECK_ARG(!a.pre || a.up2x || (a.ks == 3 && a.stride <= 1 && !a.Hin && !a.Win), "conv: a pre-activation addend is served for 3x3 stride-1 convolutions only");
     S3D_CHECK_ARG(!a.pre || a.out_mode != S3D_OUT_CONVT, "conv: a pre-activation addend with a ConvTranspose output");
     S3D_CHECK_ARG(!a.pre || !a.splitk_ws, "conv: a pre-activation addend with a split-K workspace");
     S3D_CHECK_ARG(!a.pre || !a.gn.table, "conv: a pre-activation addend with a fused GroupNorm");
     S3D_CHECK_ARG(!a.pre || (a.pre_bdiv >= 1 && a.pre_bmod >= 0), "conv: addend image rule bdiv %d bmod %d", a.pre_bdiv, a.pre_bmod);
+    // The composed ConvTranspose -> 3x3 is its own 2x2 form on the low-resolution grid with its own kernels.  Not served with it:
+    // split-K, a fused GroupNorm, the ConvTranspose scatter or NCHW, a second or broadcast source, any epilogue beyond scale / shift / ReLU
+    if (a.up2x) {
+        S3D_CHECK_ARG(a.ks == 2 && a.stride <= 1 && !a.Hin && !a.Win, "conv: the composed ConvTranspose -> 3x3 is a 2x2 stride-1 form (ks %d)", a.ks);
+        S3D_CHECK_ARG(!a.splitk_ws && !a.splits_out, "conv: the composed ConvTranspose -> 3x3 with a split-K workspace");
+        S3D_CHECK_ARG(!a.gn.table, "conv: the composed ConvTranspose -> 3x3 with a fused GroupNorm");
+        S3D_CHECK_ARG(a.out_mode == S3D_OUT_NHWC && a.cout_store == a.CoutPad, "conv: the composed ConvTranspose -> 3x3 stores NHWC, all channels");
+        S3D_CHECK_ARG(a.pre && a.pre_tab, "conv: the composed ConvTranspose -> 3x3 needs its addend and its border-class table");
+        S3D_CHECK_ARG(a.nsrc == 1 && !a.src[0].sbcast && a.src[0].C % 32 == 0 && a.CoutPad % 32 == 0 && a.KU == a.src[0].C / 4,
+                      "conv: the composed ConvTranspose -> 3x3 takes one plain source (C %d, Cout %d, KU %d)", a.src[0].C, a.CoutPad, a.KU);
+        S3D_CHECK_ARG(!a.pad_origin && a.out_cstride >= a.CoutPad && a.src[0].bdiv >= 1 && a.src[0].bmod >= 0 && a.pre_bdiv >= 1 && a.pre_bmod >= 0,
+                      "conv: the composed ConvTranspose -> 3x3: pad_origin %d, channel stride %d < %d, or a bad image rule", a.pad_origin, a.out_cstride, a.CoutPad);
+        S3D_CHECK_ARG(a.drop.p <= 0.f && !a.gate && !a.residual && !a.out_accumulate && (a.act == S3D_ACT_NONE || a.act == S3D_ACT_RELU),
+                      "conv: the composed ConvTranspose -> 3x3 takes scale / shift / ReLU only");
+        return launch_conv_up2x(a, stream);
+    }
+    S3D_CHECK_ARG(!a.pre_tab, "conv: a border-class table without the composed ConvTranspose -> 3x3");
     if (conv3x3_lds_eligible(a)) return launch_conv3x3_lds(a, stream);
     S3D_CHECK_ARG(!a.gn.table, "conv: a fused GroupNorm needs the LDS-staged 3x3 kernel (ks 3, stride 1, channel counts multiples of 32)");
     if (conv1x1_small_eligible(a)) {
@@ -1562,6 +1867,56 @@ int launch_pack(const PackArgs& a, hipStream_t stream) {
     const long total = (long)(a.n_pad / 16) * a.ku_seg * 256;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(pack_frag_kernel, dim3(blocks), dim3(256), 0, stream, a);
+    S3D_LAUNCH_CHECK();
+    return 0;
+}
+
+// ConvTranspose2d(2x2, stride 2) composed with the 3x3 over its output (conv.h, launch_upconv_compose).
+// Output pixel (2r + py, 2c + px), tap (dy, dx) of the 3x3 reads ConvT output pixel (2r + py + dy, 2c + px + dx), which is
+// quadrant ((py + dy) mod 2, (px + dx) mod 2) of low-res pixel (r + floor((py + dy) / 2), c + floor((px + dx) / 2)).
+// One thread per element of wc; a block shares (parity, co), so the 3x3's weights are broadcast loads.
+__global__ __launch_bounds__(256) void upconv_compose_kernel(const float* __restrict__ wt, const float* __restrict__ w1, int C, int Ct,
+                                                             int cin_tot, int cin_begin, float* __restrict__ wc) {
+    const int row = blockIdx.x;   // (2 py + px) * Ct + co
+    const int par = row / Ct, co = row - par * Ct, py = par >> 1, px = par & 1;
+    for (int i = threadIdx.x; i < 4 * C; i += 256) {
+        const int ci = i >> 2, a = (i >> 1) & 1, b = i & 1;
+        double s = 0.0;
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int ty = py + dy;
+            if ((ty + 2) / 2 - 1 != py - 1 + a) continue;
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int tx = px + dx;
+                if ((tx + 2) / 2 - 1 != px - 1 + b) continue;
+                const float* t = wt + (size_t)ci * Ct * 4 + (ty & 1) * 2 + (tx & 1);
+                const float* w = w1 + ((size_t)co * cin_tot + cin_begin) * 9 + (dy + 1) * 3 + dx + 1;
+                for (int cm = 0; cm < Ct; ++cm) s += (double)t[cm * 4] * (double)w[cm * 9];
+            }
+        }
+        wc[(size_t)row * 4 * C + i] = (float)s;
+    }
+}
+// tb[cy][cx][co] = sum over cm and the in-bounds taps of bt[cm] * w1[co][cin_begin + cm][tap]; class 0: the first row / column
+// (tap -1 is padding), 2: the last (tap +1 is), 1: interior
+__global__ void upconv_bias_table_kernel(const float* __restrict__ bt, const float* __restrict__ w1, int Ct, int cin_tot, int cin_begin,
+                                         float* __restrict__ tb) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 9 * Ct) return;
+    const int co = i % Ct, cls = i / Ct, cy = cls / 3, cx = cls - cy * 3;
+    double s = 0.0;
+    for (int dy = (cy == 0 ? 0 : -1); dy <= (cy == 2 ? 0 : 1); ++dy)
+        for (int dx = (cx == 0 ? 0 : -1); dx <= (cx == 2 ? 0 : 1); ++dx) {
+            const float* w = w1 + ((size_t)co * cin_tot + cin_begin) * 9 + (dy + 1) * 3 + dx + 1;
+            for (int cm = 0; cm < Ct; ++cm) s += (double)bt[cm] * (double)w[cm * 9];
+        }
+    tb[i] = (float)s;
+}
+int launch_upconv_compose(const float* wt, const float* bt, const float* w1, int C, int Ct, int cin_tot, int cin_begin, float* wc,
+                          float* tb, hipStream_t stream) {
+    S3D_CHECK_ARG(wt && bt && w1 && wc && tb && C >= 1 && Ct >= 1 && cin_begin >= 0 && cin_begin + Ct <= cin_tot, "upconv_compose: bad argument");
+    hipLaunchKernelGGL(upconv_compose_kernel, dim3(4 * Ct), dim3(256), 0, stream, wt, w1, C, Ct, cin_tot, cin_begin, wc);
+    S3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(upconv_bias_table_kernel, dim3((9 * Ct + 127) / 128), dim3(128), 0, stream, bt, w1, Ct, cin_tot, cin_begin, tb);
     S3D_LAUNCH_CHECK();
     return 0;
 }

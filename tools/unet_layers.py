@@ -3,8 +3,9 @@ tools/unet_layers_run.py, against the per-layer FLOP table of BASELINE.md sectio
 
     rocprofv3 --kernel-trace -d /tmp/ul -o u -- python tools/unet_layers_run.py ; python tools/unet_layers.py <db> [B]
 The encode launches its layers in a fixed order (api.hip: 13 encoder convs with BN+ReLU+pool after the taps, trans_c,
-the latent's broadcast add, then trans_up / skip-half 3x3 (both once per image) / ConvT / up-half 3x3 / 3x3 per up stage, up1 with its
-table kernel after the up-half 3x3); a split-K layer adds a conv_splitk_finish_kernel right after its conv."""
+the latent's broadcast add, then per up stage trans_up / skip-half 3x3 (both once per image), up1's ConvT / up-half 3x3 / table kernel
+(per image) or up2..up4's composed ConvT -> up-half 3x3 (one launch on the low-resolution map), and the second 3x3); a split-K layer
+adds a conv_splitk_finish_kernel right after its conv."""
 import sqlite3
 import sys
 
@@ -22,12 +23,13 @@ UP = []
 for i, (c, r) in enumerate(((512, 32), (256, 64), (128, 128), (64, 256))):
     one = i == 0
     UP += [("up%d skip 1x1 %d->%d @%d (per image)" % (i + 1, c, c // 2, r), 3.22 / 12),
-           ("up%d skip-half 3x3 %d->%d @%d (per image)" % (i + 1, c // 2, c // 2, r), 28.99 / 2 / 12),
-           ("up%d ConvT %d->%d%s" % (i + 1, c, c // 2, " (per image)" if one else ""), 3.22 / (12 if one else 1)),
-           ("up%d up-half 3x3 %d->%d @%d + per-image term%s" % (i + 1, c // 2, c // 2, r, " (per image)" if one else ""),
-            28.99 / 2 / (12 if one else 1))]
+           ("up%d skip-half 3x3 %d->%d @%d (per image)" % (i + 1, c // 2, c // 2, r), 28.99 / 2 / 12)]
     if one:
-        UP += [("up1 + slice table, BN, ReLU -> 12 slices", 0.0)]
+        UP += [("up1 ConvT %d->%d (per image)" % (c, c // 2), 3.22 / 12),
+               ("up1 up-half 3x3 %d->%d @%d + per-image term (per image)" % (c // 2, c // 2, r), 28.99 / 2 / 12),
+               ("up1 + slice table, BN, ReLU -> 12 slices", 0.0)]
+    else:   # K = 4 C per output pixel instead of 9 C / 2: 8 / 9 of the up-half 3x3's products, and no ConvT
+        UP += [("up%d ConvT o up-half 3x3 composed, %d@%d -> %d@%d + per-image term" % (i + 1, c, r // 2, c // 2, r), 28.99 / 2 * 8 / 9)]
     UP += [("up%d 3x3 %d->%d @%d" % (i + 1, c // 2, c // 2, r), 14.50)]
 LAYERS = ENC + [("trans_c 1x1 512->512 @16 (per image)", 2.01 * 512 / 640 / 12), ("latent = per image + slice vector -> 12 slices", 0.0)] + UP
 
@@ -35,7 +37,7 @@ LAYERS = ENC + [("trans_c 1x1 512->512 @16 (per image)", 2.01 * 512 / 640 / 12),
 def main(path, batch):
     db = sqlite3.connect(path)
     rows = db.execute("select name, start, end from kernels order by start").fetchall()
-    conv_like = lambda n: ("conv3x3_lds" in n or "conv_igemm" in n or "lin_rows" in n or "conv3x3_first" in n or "slice_bcast_add" in n
+    conv_like = lambda n: ("conv3x3_lds" in n or "conv_up2x_lds" in n or "conv_igemm" in n or "lin_rows" in n or "conv3x3_first" in n or "slice_bcast_add" in n
                            or "slice_table_act" in n)
     encodes, cur = [], None
     for name, st, en in rows:
