@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define S3D_VERSION 121          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding; 119: s3d_mesh_render_*; 120: s3d_unet_encode_fwd computes the decoder's slice-invariant terms once per image, the weights-only ones in s3d_unet_pack (other packed-image and workspace sizes: query them); 121: up2-up4 run ConvTranspose and the first 3x3's up half as one convolution of the low-resolution map with weights composed in s3d_unet_pack (packed-image and workspace sizes change again) */
+#define S3D_VERSION 122          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding; 119: s3d_mesh_render_*; 120: s3d_unet_encode_fwd computes the decoder's slice-invariant terms once per image, the weights-only ones in s3d_unet_pack (other packed-image and workspace sizes: query them); 121: up2-up4 run ConvTranspose and the first 3x3's up half as one convolution of the low-resolution map with weights composed in s3d_unet_pack (packed-image and workspace sizes change again); 122: s3d_mesh_simplify_* */
 #define S3D_E_ARG (-1)           /* bad argument / unsupported shape */
 #define S3D_E_WORKSPACE (-2)     /* workspace or packed-weight buffer too small */
 
@@ -713,6 +713,43 @@ int s3d_mesh_render_render(long n_vertices, const long long* faces, long n_faces
                            const void* workspace, size_t workspace_bytes, const int* entries, long n_entries,
                            const double* vertex_colors, double* depth, int* face, unsigned char* rgba,
                            unsigned long long* n_tests, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh simplification (mesh_simplify.hip; slice3d_amd/mesh_simplify.py, reg_slices/simplify_meshes.py): quadric
+ * edge collapse with the parameters of the reference's libsimplify (src_convonet/utils/libsimplify/Simplify.h), in
+ * rounds of independent collapses.  Mesh conventions as above; quadrics, costs and positions are float64.
+ *
+ * A pass: vertex -> face lists ordered by face index; face normals; in the first pass the vertex quadrics (afterwards a
+ * collapse adds the removed vertex's quadric to the kept one); border flags (a vertex with an edge that has exactly one
+ * face); per undirected edge the reference's cost and target (the quadric minimiser when the 3x3 system is regular and
+ * the endpoints are no border vertices, else the best of the endpoints and the midpoint).  An edge is a candidate when
+ * its cost <= 1e-9 (k + 3)^aggressiveness, both endpoints carry the same border flag, no face around either endpoint
+ * would flip or degenerate (the reference's `flipped`, against the faces' current normals) and the link condition holds
+ * (a vertex next to both endpoints is an apex of a face on the edge: two apexes for an interior edge, one for a border
+ * edge; no two surviving faces would coincide; no interior edge between two border vertices).  Every candidate writes a
+ * 64-bit key (the cost's sign, exponent and two mantissa bits | a bijective mix of the edge id) by integer atomicMin into
+ * all vertices of the faces around its endpoints and wins if it still holds the minimum at both endpoints; winners touch
+ * disjoint faces.  All winners are applied, or, when they would pass the target, the cheapest ones that reach it, so
+ * n_faces_out is target_faces or one below it (an interior collapse removes two faces) unless the rounds run out first.
+ * A round is four passes at one k, then the compaction of the face list and the read-back of the live count; k starts
+ * at 0 and advances after a round that removed under 1/8 of the faces; at most 100 rounds, the reference's bound.
+ * Closed oriented manifold in -> closed oriented manifold of the same genus out.  The output is the same bits from run
+ * to run: no float atomics, every float64 sum in one fixed order.
+ *   run:  validates the indices with a kernel of its own before anything dereferences them (S3D_E_ARG with a message
+ *         for an index outside [0, n_vertices)), simplifies inside the workspace and returns the counts.  One stream
+ *         synchronisation per round.  S3D_E_ARG with a message for n_faces == 0, target_faces < 0 or a workspace below
+ *         s3d_mesh_simplify_workspace_bytes(n_vertices, n_faces).  target_faces >= n_faces runs no round: the faces
+ *         come back as they are.  Faces that name a vertex twice are dropped before the first round.
+ *   emit: vertices_out (n_vertices_out, 3): the vertices still referenced, in ascending original index; faces_out
+ *         (n_faces_out, 3) in ascending original face index.  n_vertices / n_faces are the INPUT sizes, as in run.
+ * workspace_bytes returns 0 for sizes it cannot serve (n_faces < 1 or >= 2^29, n_vertices < 1 or >= 2^31).
+ * ------------------------------------------------------------------------------------------- */
+size_t s3d_mesh_simplify_workspace_bytes(long n_vertices, long n_faces);
+int s3d_mesh_simplify_run(const double* vertices, long n_vertices, const long long* faces, long n_faces,
+                          long target_faces, double aggressiveness, void* workspace, size_t workspace_bytes,
+                          long* n_vertices_out, long* n_faces_out, int* n_rounds, void* stream);
+int s3d_mesh_simplify_emit(const void* workspace, size_t workspace_bytes, long n_vertices, long n_faces,
+                           double* vertices_out, long long* faces_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Dataset staging on the device — the per-sample tensor work of Slice3DDataset.__getitem__

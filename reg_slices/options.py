@@ -72,6 +72,9 @@ _BUILD_FLAGS = [
                                                  "instead of reading 04_img_slices_gen")),
     ("ddim_steps", dict(type=int, default=200, help="[build] DDIM steps of the in-memory gen route")),
     ("gen_seed", dict(type=int, default=0, help="[build] seed of the in-memory gen route's noise")),
+    ("simplify_nfaces", dict(type=int, default=None, help="[build] reconstruct.py: simplify every mesh to about this many "
+                                                         "faces on the GPU before export (slice3d_amd/mesh_simplify.py, "
+                                                         "the reference's Generator3D(simplify_nfaces=...))")),
 ]
 
 

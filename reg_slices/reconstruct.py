@@ -3,7 +3,7 @@ load a checkpoint into Slices3DRegModel(mode='test'), run Generator3D (MISE or d
 -> marching cubes) per test object and export `<shape>.obj`, with the reference's flags.
 
     python reg_slices/reconstruct.py --name_exp demo --name_ckpt x.ckpt --name_dataset synthetic \
-        --mode test --img_size 128 --mc_res0 64 --mc_up_steps 2
+        --mode test --img_size 128 --mc_res0 64 --mc_up_steps 2 [--simplify_nfaces 10000]
 
 With --name_model gtslice --from_which_slices gen --gen_ckpt <LatentDiffusion .ckpt> the slices are generated in memory
 (slice3d_amd/gen_route.py): per batch of --n_bs test objects, input view 004 -> SliceDiffusion.generate -> the 8-bit mosaic
@@ -12,6 +12,7 @@ gives it, without writing or reading slice images.
 """
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -23,6 +24,19 @@ from options import get_parser  # noqa: E402
 from slice3d_amd.generator import Generator3D  # noqa: E402
 from slice3d_amd.models import Slices3DRegModel  # noqa: E402
 from slice3d_amd.synth import SyntheticSlice3DDataset  # noqa: E402
+
+
+def export_mesh(args, mesh, stats, path_mesh):
+    """--simplify_nfaces N: simplify_mesh(mesh, N, 5.) as the reference's Generator3D.extract_mesh does (reconstruct.py:231-235
+    there), on the GPU; then `<shape>.obj`."""
+    if args.simplify_nfaces is not None and len(mesh.faces):
+        from slice3d_amd.mesh_simplify import simplify_mesh
+        torch.cuda.synchronize()
+        t0 = time.time()
+        mesh = simplify_mesh(mesh, args.simplify_nfaces, 5.)
+        stats["time (simplify)"] = time.time() - t0
+    mesh.export(path_mesh)
+    print(path_mesh, "%d verts %d faces" % (len(mesh.vertices), len(mesh.faces)), stats)
 
 
 def main():
@@ -67,8 +81,7 @@ def main():
                 continue
             data = {k: v.unsqueeze(0).cuda() for k, v in dataset[idx].items()}
             mesh, stats = generator.generate_mesh(data)
-            mesh.export(path_mesh)
-            print(path_mesh, "%d verts %d faces" % (len(mesh.vertices), len(mesh.faces)), stats)
+            export_mesh(args, mesh, stats, path_mesh)
 
 
 def reconstruct_generated(args, generator, path_res):
@@ -100,8 +113,7 @@ def reconstruct_generated(args, generator, path_res):
                 data = {k: v.unsqueeze(0).cuda() for k, v in dataset[idx].items()}
                 data["img_slices"] = img_slices[j:j + 1]
                 mesh, stats = generator.generate_mesh(data)
-                mesh.export(path_mesh)
-                print(path_mesh, "%d verts %d faces" % (len(mesh.vertices), len(mesh.faces)), stats)
+                export_mesh(args, mesh, stats, path_mesh)
 
 
 if __name__ == "__main__":

@@ -215,6 +215,10 @@ SYMBOLS = {
     "s3d_mesh_render_build": (_i, [_vp, _l, _vp, _l, C.POINTER(C.c_double), _i, _i, _i, _vp, _sz, C.POINTER(C.c_long), _vp]),
     "s3d_mesh_render_fill": (_i, [_l, _l, _i, _i, _i, _vp, _sz, _vp, _l, _vp]),
     "s3d_mesh_render_render": (_i, [_l, _vp, _l, _i, _i, _i, _vp, _sz, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "s3d_mesh_simplify_workspace_bytes": (_sz, [_l, _l]),
+    "s3d_mesh_simplify_run": (_i, [_vp, _l, _vp, _l, _l, C.c_double, _vp, _sz, C.POINTER(C.c_long), C.POINTER(C.c_long),
+                                   C.POINTER(C.c_int), _vp]),
+    "s3d_mesh_simplify_emit": (_i, [_vp, _sz, _l, _l, _vp, _vp, _vp]),
     "s3d_dataset_images_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "s3d_dataset_points_fwd": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _vp]),
     "s3d_nchw_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
