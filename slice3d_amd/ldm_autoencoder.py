@@ -5,9 +5,9 @@ configs/latent-diffusion/objaverse-ldm-kl-8-infer.yaml) and of its condition enc
 Inference only.  The module trees give the reference's state_dict keys (encoder.down.N.block.M.norm1.weight,
 decoder.up.N.upsample.conv.weight, decoder.mid.attn_1.q.weight, quant_conv.*, post_quant_conv.*; conv1_2.* ... conv_last.*,
 classifier.*, trans1_2.* ... trans5_3.*, mean, std).  Every convolution, GroupNorm, attention and resampling step is an entry
-point of libslice3d_hip.so, on channels-last activations, as in ldm_unet.py; there is no CPU fallback.  Host code only moves
-tensors between layouts (the 4 x 4 latent mosaic, the 4 x 4 repeat of the condition maps) and draws the posterior sample of a
-16 x 16 x 4 latent.
+point of libslice3d_hip.so, on channels-last activations, through the operator layer shared with the U-Net (ldm_ops.LdmOps);
+there is no CPU fallback.  Host code only moves tensors between layouts (the 4 x 4 latent mosaic, the 4 x 4 repeat of the
+condition maps) and draws the posterior sample of a 16 x 16 x 4 latent.
 """
 import ctypes as C
 import types
@@ -16,8 +16,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .ldm_unet import UNetModel
-from .models import HipModel, data_ptr
+from .ldm_ops import LdmOps
+from .models import data_ptr
 from .models_gt import VGG16BNFeats, gt_encoder_params
 
 KL_F8 = dict(double_z=True, z_channels=4, resolution=512, in_channels=3, out_ch=3, ch=128, ch_mult=[1, 2, 4, 4],
@@ -162,37 +162,14 @@ def tile_condition(z):
     return z.repeat(1, 1, 4, 4)
 
 
-class _LdmOps(HipModel):
-    """The U-Net's channels-last primitive wrappers (ldm_unet.UNetModel), shared by the first-stage modules."""
-    _conv = UNetModel._conv
-    _group_norm = UNetModel._group_norm
-    _gn_table = UNetModel._gn_table
-    _gn_conv_apply = UNetModel._gn_conv_apply
-    _gn_conv_served = UNetModel._gn_conv_served
-    _gn_conv_fusable = UNetModel._gn_conv_fusable
-    _take_pending = UNetModel._take_pending
-    _finish_pending = UNetModel._finish_pending
-    _resample = UNetModel._resample
-    _to_nhwc = UNetModel._to_nhwc
-    _pack_conv = UNetModel._pack_conv
-    _pad16 = staticmethod(UNetModel._pad16)
+class _FirstStageOps(LdmOps):
+    """What the first stage and the condition encoder add to the operator layer: their blocks' packing and forwards."""
     _NOT_EVAL = "call model.eval(): inference only"
+    _BAD_PREC = "prec must be 'f32' or 'f16x3'"
+    _PRECS = ("f16x3", "f32")
 
-    def _init_ops(self, backend, prec, fuse_gn=True):
-        if prec not in ("f32", "f16x3"):
-            raise ValueError("prec must be 'f32' or 'f16x3'")
-        self.backend, self.prec, self.fuse_gn = backend, prec, fuse_gn
-        self._lib = _lib.load() if backend == "hip" else None
-        self._packed, self._packed_key, self._ws, self._ws_side, self._pending = {}, None, None, None, None
-        self.defer_finish = False
-        self._extra = {}
-
-    def _precv(self):
-        return _lib.prec_code(self.prec, ("f16x3", "f32"))
-
-    def _params_key(self):
-        return (self.fuse_gn, self.prec) + tuple((p.data_ptr(), p._version) for p in
-                                                 list(self.parameters()) + list(self.buffers()))
+    def _pack_module(self, conv):
+        self._pack_conv(conv, conv.weight, conv.bias)
 
     def _pack_padded(self, conv, cout_pad):
         """conv with its output channels padded with zero rows to cout_pad (so the next layer reads a 16-channel pitch)."""
@@ -200,35 +177,21 @@ class _LdmOps(HipModel):
         wp = torch.zeros((cout_pad,) + tuple(w.shape[1:]), dtype=w.dtype, device=w.device)
         bp = torch.zeros((cout_pad,), dtype=w.dtype, device=w.device)
         wp[:w.shape[0]], bp[:w.shape[0]] = w, b
-        ns = types.SimpleNamespace(weight=wp, bias=bp)
-        self._extra[id(conv)] = ns
-        self._packed[id(ns)] = self._pack_conv(ns)
-
-    def _pack_attn(self, blk):
-        wqkv = torch.cat([blk.q.weight, blk.k.weight, blk.v.weight], 0).contiguous()
-        bqkv = torch.cat([blk.q.bias, blk.k.bias, blk.v.bias], 0).contiguous()
-        ns = types.SimpleNamespace(weight=wqkv, bias=bqkv)
-        self._extra[id(blk)] = ns
-        self._packed[id(ns)] = self._pack_conv(ns)
-        self._packed[id(blk.proj_out)] = self._pack_conv(blk.proj_out)
+        self._pack_conv((conv, "padded"), wp, bp)
 
     def _pack_tree(self, root):
         for mod in root.modules():
             if isinstance(mod, ResnetBlock):
                 for conv in (mod.conv1, mod.conv2) + ((mod.nin_shortcut,) if hasattr(mod, "nin_shortcut") else ()):
-                    self._packed[id(conv)] = self._pack_conv(conv)
+                    self._pack_module(conv)
             elif isinstance(mod, AttnBlock):
-                self._pack_attn(mod)
+                self._pack_conv((mod, "qkv"), torch.cat([mod.q.weight, mod.k.weight, mod.v.weight], 0).contiguous(),
+                                torch.cat([mod.q.bias, mod.k.bias, mod.v.bias], 0).contiguous())
+                self._pack_module(mod.proj_out)
             elif isinstance(mod, _Resample):
-                self._packed[id(mod.conv)] = self._pack_conv(mod.conv)
+                self._pack_module(mod.conv)
 
     # -- blocks ----------------------------------------------------------------------------------
-    def _gn_conv(self, gn, conv, x, residual=None):
-        """conv(swish(GroupNorm(x))) (+ residual): one fused operator where s3d_conv_gn_fwd serves the shape."""
-        if self._gn_conv_fusable(conv, x):
-            return self._gn_conv_apply(conv, x, None, self._gn_table(gn, x), residual=residual)
-        return self._conv(conv, self._group_norm(gn, x, silu=True), residual=residual)
-
     def _resnet(self, blk, x):
         """ResnetBlock.forward (model.py:117-141) with temb None; the shortcut is conv2's residual epilogue."""
         h = self._gn_conv(blk.norm1, blk.conv1, x)
@@ -238,33 +201,20 @@ class _LdmOps(HipModel):
     def _attn(self, blk, x):
         """AttnBlock.forward (model.py:181-202): q | k | v as one 1x1 convolution, one wide head, proj_out + residual."""
         n, h, w, c = x.shape
-        hn = self._group_norm(blk.norm, x, silu=False)
-        qkv = self._conv(self._extra[id(blk)], hn)
+        qkv = self._conv((blk, "qkv"), self._group_norm(blk.norm, x, silu=False))
         att = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
         _lib.check(self._lib.s3d_wide_attention_fwd(qkv.data_ptr(), att.data_ptr(), n, h * w, c, self._precv(), self._stream()),
                    "s3d_wide_attention_fwd")
         return self._conv(blk.proj_out, att, residual=x)
 
     def _downsample(self, ds, x):
-        n, h, w, c = x.shape
-        ho, wo = (h - 2) // 2 + 1, (w - 2) // 2 + 1
-        out = torch.empty((n, ho, wo, c), dtype=torch.float32, device=x.device)
-        buf, cout, cin, _, ks = self._packed[id(ds.conv)]
-        _lib.check(self._lib.s3d_conv_strided_fwd(buf.data_ptr(), x.data_ptr(), out.data_ptr(), n, h, w, ho, wo, cout, cin, ks, 2,
-                                                  1, self._precv(), self._stream()), "s3d_conv_strided_fwd")
-        return out
+        return self._conv_strided(ds.conv, x, (x.shape[1] - 2) // 2 + 1, (x.shape[2] - 2) // 2 + 1, 2, 1)
 
     def _mid_fwd(self, mid, h):
         return self._resnet(mid.block_2, self._attn(mid.attn_1, self._resnet(mid.block_1, h)))
 
-    def _to_nchw(self, x, c=None):
-        n, h, w, cs = x.shape
-        out = torch.empty((n, cs, h, w), dtype=torch.float32, device=x.device)
-        _lib.check(self._lib.s3d_nhwc_to_nchw(x.data_ptr(), out.data_ptr(), n, cs, h, w, self._stream()), "s3d_nhwc_to_nchw")
-        return out[:, :c] if c is not None else out
 
-
-class AutoencoderKL(_LdmOps, nn.Module):
+class AutoencoderKL(_FirstStageOps, nn.Module):
     _NO_LIB = "AutoencoderKL(backend=%r) cannot compute: the HIP library is required; there is no CPU fallback"
 
     def __init__(self, ddconfig=KL_F8, embed_dim=4, backend="hip", prec="f16x3", fuse_gn=True):
@@ -276,7 +226,7 @@ class AutoencoderKL(_LdmOps, nn.Module):
         self.decoder = Decoder(**ddconfig)
         self.quant_conv = nn.Conv2d(2 * ddconfig["z_channels"], 2 * embed_dim, 1)
         self.post_quant_conv = nn.Conv2d(embed_dim, ddconfig["z_channels"], 1)
-        self._init_ops(backend, prec, fuse_gn)
+        self._init_ops(backend, prec, self._PRECS, fuse_gn)
 
     def _device(self):
         return self.quant_conv.weight.device
@@ -284,10 +234,10 @@ class AutoencoderKL(_LdmOps, nn.Module):
     def repack(self):
         self._require_lib()
         self._check_packable()
-        self._packed, self._extra = {}, {}
+        self._packed = {}
         for tree in (self.encoder, self.decoder):
             self._pack_tree(tree)
-            self._packed[id(tree.conv_in)] = self._pack_conv(tree.conv_in)
+            self._pack_module(tree.conv_in)
         # layers whose output feeds a convolution with fewer than 16 channels, or the 3-channel image: padded output rows
         self._pack_padded(self.encoder.conv_out, self._pad16(self.encoder.conv_out.weight.shape[0]))
         self._pack_padded(self.quant_conv, self._pad16(self.quant_conv.weight.shape[0]))
@@ -296,7 +246,7 @@ class AutoencoderKL(_LdmOps, nn.Module):
         self._packed_key = self._params_key()
 
     def _padded_conv(self, conv, x):
-        return self._conv(self._extra[id(conv)], x)
+        return self._conv((conv, "padded"), x)
 
     def _begin(self):
         self._require_lib()
@@ -355,7 +305,7 @@ class AutoencoderKL(_LdmOps, nn.Module):
 _TRANS = (("trans1_2", 64, 192), ("trans2_2", 128, 384), ("trans3_3", 256, 384), ("trans4_3", 512, 768), ("trans5_3", 512, 768))
 
 
-class ImageEncoderVGG16BN(_LdmOps, VGG16BNFeats):
+class ImageEncoderVGG16BN(_FirstStageOps, VGG16BNFeats):
     """modules.py:204-267: VGG16-BN pre-BatchNorm taps conv1_2 ... conv5_3, 1x1 trans* projections, nearest resize to
     16 / 8 / 4 / 2 / 1 and a 4 x 4 repeat -> the U-Net's c_fmaps f1 ... f5."""
     _NO_LIB = "ImageEncoderVGG16BN(backend=%r) cannot compute: the HIP library is required; there is no CPU fallback"
@@ -366,8 +316,7 @@ class ImageEncoderVGG16BN(_LdmOps, VGG16BNFeats):
             setattr(self, name, nn.Conv2d(cin, cout, 1))
         self.register_buffer("mean", torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1))
         self.register_buffer("std", torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1))
-        self._init_ops(backend, prec)
-        self._ws = {}      # HipModel._workspace: the VGG16-BN encoder's scratch
+        self._init_ops(backend, prec, self._PRECS)
 
     def _device(self):
         return self.trans1_2.weight.device
@@ -377,7 +326,9 @@ class ImageEncoderVGG16BN(_LdmOps, VGG16BNFeats):
         self._check_packable()
         self._enc_packed = self._pack("s3d_gt_encoder_pack", gt_encoder_params(types.SimpleNamespace(img_encoder=self), data_ptr),
                                       lib.s3d_gt_encoder_packed_bytes())
-        self._packed = {id(getattr(self, name)): self._pack_conv(getattr(self, name)) for name, _, _ in _TRANS}
+        self._packed = {}
+        for name, _, _ in _TRANS:
+            self._pack_module(getattr(self, name))
         self._packed_key = self._params_key()
 
     @torch.no_grad()
@@ -403,11 +354,7 @@ class ImageEncoderVGG16BN(_LdmOps, VGG16BNFeats):
         _lib.check(lib.s3d_gt_encode_fwd(self._enc_packed.data_ptr(), xn.data_ptr(), C.byref(pyr), n, s, self._precv(),
                                          ws.data_ptr(), nb, self._stream()), "s3d_gt_encode_fwd")
         out, stride = {}, s // 16     # F.interpolate(size=16 >> l) of an (s >> l)-wide map: every stride-th pixel from 0
-        for l, (name, cin, cout) in enumerate(_TRANS):
-            buf = self._packed[id(getattr(self, name))][0]
-            r = 16 >> l
-            t = torch.empty((n, r, r, cout), dtype=torch.float32, device=x.device)
-            _lib.check(lib.s3d_conv_strided_fwd(buf.data_ptr(), levels[l].data_ptr(), t.data_ptr(), n, s >> l, s >> l, r, r,
-                                                cout, cin, 1, stride, 0, self._precv(), self._stream()), "s3d_conv_strided_fwd")
+        for l, (name, _, _) in enumerate(_TRANS):
+            t = self._conv_strided(getattr(self, name), levels[l], 16 >> l, 16 >> l, stride, 0)
             out["f%d" % (l + 1)] = self._to_nchw(t).repeat(1, 1, 4, 4)
         return out

@@ -217,8 +217,9 @@ def vgg_params(model, pick):
 
 class HipModel:
     """Engine plumbing of the models that compute through libslice3d_hip.so.  A model supplies `_device()`, `backend`,
-    `_lib` (None without the library), the `_ws` dict and the texts `_NO_LIB` (% backend) and `_NOT_EVAL`.  UNetModel
-    uses the library / eval / stream / repack-on-change parts, with a `_params_key` of its own."""
+    `_lib` (None without the library), the `_ws` dict of `_workspace`, `repack()` with `_packed_key`, and the texts
+    `_NO_LIB` (% backend) and `_NOT_EVAL`.  The latent-diffusion models get all of that state from ldm_ops.LdmOps, the
+    operator layer built on this class."""
 
     def _require_lib(self):
         if self._lib is None:
@@ -232,10 +233,13 @@ class HipModel:
     def _stream(self):
         return _lib.stream_ptr(self._device())
 
-    def _workspace(self, key, nbytes):
+    def _workspace(self, key, nbytes, device=None):
+        """The scratch buffer `key`, at least nbytes long, on `device` (a caller on a hot path passes the device of the
+        tensors it serves; default: the model's, which costs a walk to a parameter)."""
+        dev = device if device is not None else self._device()
         buf = self._ws.get(key)
-        if buf is None or buf.numel() < nbytes or buf.device != self._device():
-            buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self._device())
+        if buf is None or buf.numel() < nbytes or buf.device != dev:
+            buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
             self._ws[key] = buf
         return buf
 
@@ -243,7 +247,9 @@ class HipModel:
         return t.to(device=self._device(), dtype=torch.float32).contiguous()
 
     def _params_key(self):
-        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
+        # (address, version) of every parameter and buffer, in ONE walk over the modules: every forward pays for this
+        return tuple((t.data_ptr(), t._version) for m in self.modules() for d in (m._parameters, m._buffers)
+                     for t in d.values() if t is not None)
 
     def _ensure_packed(self):
         if self._packed_key is None or self._packed_key != self._params_key():
