@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define S3D_VERSION 122          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding; 119: s3d_mesh_render_*; 120: s3d_unet_encode_fwd computes the decoder's slice-invariant terms once per image, the weights-only ones in s3d_unet_pack (other packed-image and workspace sizes: query them); 121: up2-up4 run ConvTranspose and the first 3x3's up half as one convolution of the low-resolution map with weights composed in s3d_unet_pack (packed-image and workspace sizes change again); 122: s3d_mesh_simplify_* */
+#define S3D_VERSION 123          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding; 119: s3d_mesh_render_*; 120: s3d_unet_encode_fwd computes the decoder's slice-invariant terms once per image, the weights-only ones in s3d_unet_pack (other packed-image and workspace sizes: query them); 121: up2-up4 run ConvTranspose and the first 3x3's up half as one convolution of the low-resolution map with weights composed in s3d_unet_pack (packed-image and workspace sizes change again); 122: s3d_mesh_simplify_*; 123: s3d_conv_plan_describe */
 #define S3D_E_ARG (-1)           /* bad argument / unsupported shape */
 #define S3D_E_WORKSPACE (-2)     /* workspace or packed-weight buffer too small */
 
@@ -379,6 +379,14 @@ int s3d_add_nchw_fwd(const float* a, const float* b, float* out, int n, int c, i
  * prec: S3D_PREC_F32 or S3D_PREC_F16X3. */
 int s3d_conv_strided_fwd(const void* packed, const float* x, float* out, int N, int Hin, int Win, int Hout, int Wout, int cout,
                          int cin, int ks, int stride, int pad_origin, int prec, void* stream);
+/* Which kernels a convolution call would launch, without launching them (version 123; no GPU needed): `buf` receives e.g.
+ * "conv3x3_small_f16x3_kernel<2,true,9> grid=2x5 block=256 splits=5 finish=1; conv_splitk_finish_kernel grid=2x1 block=256" — the
+ * kernel's name as a kernel trace prints it, its grid in workgroups, the split-K count and whether the finish pass follows.
+ * Hin = Win = stride = 0: s3d_conv_fwd, or with fused_gn s3d_conv_gn_fwd (nsplit_out_requested: called with nsplit_out).
+ * Otherwise s3d_conv_strided_fwd with (H, W) = (Hout, Wout) and cin0 = cin.  Returns 0, or the code the call would return
+ * for these arguments (s3d_last_error says why).  The description follows S3D_CONV_SMALL / S3D_CONV_SMALL_1X1 as the calls do. */
+int s3d_conv_plan_describe(int N, int H, int W, int cout, int cin0, int cin1, int ks, int prec, int fused_gn, size_t workspace_bytes,
+                           int nsplit_out_requested, int Hin, int Win, int stride, int pad_origin, char* buf, size_t buf_len);
 /* AttnBlock (model.py:150-202): one head of width C (64, 128, 256 or 512) over T >= 1 tokens, softmax(q k^T C^-0.5) v;
  * qkv (N, T, 3C) rows q | k | v -> out (N, T, C).  prec: S3D_PREC_F32 or S3D_PREC_F16X3 (both exact fp32 arithmetic). */
 int s3d_wide_attention_fwd(const float* qkv, float* out, int N, int T, int C, int prec, void* stream);

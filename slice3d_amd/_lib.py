@@ -152,6 +152,7 @@ SYMBOLS = {
     "s3d_nchw_to_nhwc_pad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "s3d_add_nchw_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "s3d_conv_strided_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "s3d_conv_plan_describe": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _sz, _i, _i, _i, _i, _i, C.c_char_p, _sz]),
     "s3d_wide_attention_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "s3d_image_normalize_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "s3d_vgg_packed_bytes": (_sz, []),

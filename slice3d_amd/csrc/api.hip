@@ -8,7 +8,7 @@
 
 #include <math.h>
 
-#include "conv.h"
+#include "conv_plan.h"
 #include "decode.h"
 #include "train.h"
 #include "ldm_ops.h"

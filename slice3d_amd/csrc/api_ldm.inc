@@ -55,16 +55,19 @@ extern "C" int s3d_conv_pack(const float* w, const float* bias, int cout, int ci
 
 // out[n,y,x,:cout] = conv(cat(x0, x1)) + bias (+ residual); x0 (N,H,W,pad16(cin0)), x1 (N,H,W,pad16(cin1)) or NULL;
 // out / residual have cout channels (channel stride cout, cout % 4 == 0).  "same" padding, stride 1.
-static int conv_fwd_impl(const void* packed, const float* x0, const float* x1, const float* residual, float* out,
+static int conv_fwd_desc(ConvLaunch& c, const void* packed, const float* x0, const float* x1, const float* residual, float* out,
                          int N, int H, int W, int cout, int cin0, int cin1, int ks, int prec, void* workspace,
-                         size_t workspace_bytes, void* stream, const ConvGn* gn, int* splits_out = nullptr) {
-    hipStream_t st = (hipStream_t)stream;
+                         size_t workspace_bytes, const ConvGn* gn, int* splits_out) {
+    if (gn)
+        S3D_CHECK_ARG(s3d_conv_gn_supported(cout, cin0, cin1, ks, prec, H, W, workspace && workspace_bytes >= sizeof(float)),
+                      "conv_gn_fwd: needs ks 3, split precision, channel counts that are multiples of 32 (at most %d inputs) and, below "
+                      "an 8 x 16 map, a split-K workspace (s3d_conv_gn_supported)", S3D_GN_CMAX);
     S3D_CHECK_ARG(packed && x0 && out && N >= 1 && H >= 1 && W >= 1 && (ks == 1 || ks == 3) && cout % 4 == 0,
                   "conv_fwd: bad arguments");
     S3D_CHECK_ARG((cin1 > 0) == (x1 != nullptr), "conv_fwd: x1 / cin1 mismatch");
     const GenConvLayout L = gen_conv_layout(cout, cin0, cin1, ks);
     const float* b = (const float*)packed;
-    ConvLaunch c = {};
+    c = {};
     c.N = N; c.H = H; c.W = W; c.ks = ks;
     c.CoutPad = L.cout_pad; c.wpk = b + L.w; c.KU = L.KU;
     const bool f16 = L.KU % 2 == 0 && cin0 % 32 == 0 && cin1 % 32 == 0;
@@ -87,7 +90,14 @@ static int conv_fwd_impl(const void* packed, const float* x0, const float* x1, c
         c.splitk_ws = (float*)workspace;
         c.splitk_floats = workspace_bytes / sizeof(float);
     }
-    return launch_conv(c, st);
+    return 0;
+}
+static int conv_fwd_impl(const void* packed, const float* x0, const float* x1, const float* residual, float* out,
+                         int N, int H, int W, int cout, int cin0, int cin1, int ks, int prec, void* workspace,
+                         size_t workspace_bytes, void* stream, const ConvGn* gn, int* splits_out = nullptr) {
+    ConvLaunch c;
+    TRY(conv_fwd_desc(c, packed, x0, x1, residual, out, N, H, W, cout, cin0, cin1, ks, prec, workspace, workspace_bytes, gn, splits_out));
+    return launch_conv(c, (hipStream_t)stream);
 }
 
 extern "C" int s3d_conv_fwd(const void* packed, const float* x0, const float* x1, const float* residual, float* out,
@@ -107,16 +117,13 @@ extern "C" int s3d_conv_gn_supported(int cout, int cin0, int cin1, int ks, int p
     if (ks != 3 || (prec != S3D_PREC_F16X3 && prec != S3D_PREC_F16)) return 0;
     if (cout <= 0 || cin0 <= 0 || cin1 < 0 || cout % 32 || cin0 % 32 || cin1 % 32) return 0;
     if (cin0 + cin1 > S3D_GN_CMAX) return 0;
-    if (H > 0 && W > 0 && (W < 16 || H < 8) && !has_workspace) return 0;   // conv3x3_lds_eligible (conv.hip)
+    if (H > 0 && W > 0 && conv_below_lds_tile(H, W) && !has_workspace) return 0;
     return 1;
 }
 extern "C" int s3d_conv_gn_fwd(const void* packed, const float* x0, const float* x1, const float* residual, float* out,
                                int N, int H, int W, int cout, int cin0, int cin1, int ks, int prec, const float* table,
                                int silu, void* workspace, size_t workspace_bytes, int* nsplit_out, void* stream) {
     S3D_CHECK_ARG(table, "conv_gn_fwd: null table");
-    S3D_CHECK_ARG(s3d_conv_gn_supported(cout, cin0, cin1, ks, prec, H, W, workspace && workspace_bytes >= sizeof(float)),
-                  "conv_gn_fwd: needs ks 3, split precision, channel counts that are multiples of 32 (at most %d inputs) and, below "
-                  "an 8 x 16 map, a split-K workspace (s3d_conv_gn_supported)", S3D_GN_CMAX);
     const ConvGn gn = {table, silu};
     // nsplit_out != NULL: a split-K launch skips its finish pass — *nsplit_out > 1 then means `out` is NOT written, the raw
     // partial sums sit in `workspace` and the caller hands them to the next GroupNorm (S3dConvPartial) or to s3d_conv_finish_fwd

@@ -12,7 +12,7 @@
 // padding taps.  fp32 MFMA runs at 256 FLOP/clk/CU, i.e. one 16-byte operand load feeds 128 cycles of
 // MFMA per (MT|NT)-fold reuse, so the operand streams fit the L1/L2 path at this precision.
 #include <stdlib.h>
-#include "conv.h"
+#include "conv_plan.h"
 #include <utility>
 #include <vector>
 
@@ -516,21 +516,7 @@ __global__ __launch_bounds__(256, 2) void lin_rows_f16x3_kernel(const ConvLaunch
     }
 }
 
-static bool lin_rows_eligible(const ConvLaunch& a) {
-    if (a.ks != 1 || a.nsrc != 1 || a.stride > 1 || !a.wpk16 || (a.KU & 1) || a.CoutPad % 32) return false;
-    if ((a.Hin && a.Hin != a.H) || (a.Win && a.Win != a.W)) return false;
-    const ConvSrc& S = a.src[0];
-    if (S.sbcast || S.bmod || S.bdiv != 1 || S.C % 32 || S.C > 128 || a.KU != S.C / 16) return false;
-    return (long)a.N * a.H * a.W >= 65536;   // short row sets stay on the tile menu (more, smaller workgroups)
-}
-static int launch_lin_rows(const ConvLaunch& a, hipStream_t stream) {
-    const long P = (long)a.N * a.H * a.W;
-    const long nblk = (P + 64 * LR_MT - 1) / (64 * LR_MT);
-    S3D_CHECK_ARG(nblk < (1L << 31), "conv grid out of range (%ld)", nblk);
-    hipLaunchKernelGGL(lin_rows_f16x3_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, a);
-    S3D_LAUNCH_CHECK();
-    return 0;
-}
+static_assert(kLinRowsTile == 64 * LR_MT, "conv_plan.h: rows of a lin_rows workgroup");
 
 // ---------------------------------------------------------------------------------------------
 // Row-linear layers on the long row sets of the training step (K and Cout multiples of 128: the attention block's in_proj
@@ -759,35 +745,6 @@ __global__ __launch_bounds__(256, 2) void lin_stream_f16x3_kernel(const ConvLaun
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's last prefetches must not outlive the workgroup's LDS
-}
-
-static bool lin_stream_eligible(const ConvLaunch& a) {
-    if (a.ks != 1 || a.nsrc != 1 || a.stride > 1 || !a.wpk16 || a.CoutPad % 32) return false;
-    if ((a.Hin && a.Hin != a.H) || (a.Win && a.Win != a.W)) return false;
-    const ConvSrc& S = a.src[0];
-    if (S.sbcast || S.bmod || S.bdiv != 1 || S.C % 128 || S.C > 384 || a.KU != S.C / 16) return false;
-    // K > 128: all 128 outputs live; plain products only (no scale / bias / output dropout)
-    if (S.C > 128 && (a.CoutPad != 128 || a.drop.p > 0.f || a.scale || a.shift)) return false;
-    // cout_store == CoutPad: the residual rows of a 32-channel output slot are requested without a per-channel guard
-    // (hand-issued loads), so every slot must lie inside the output / residual row
-    if (a.out_mode != S3D_OUT_NHWC || a.gate || a.out_accumulate || a.cout_store != a.CoutPad || a.scale) return false;
-    if (a.act != S3D_ACT_NONE && a.act != S3D_ACT_RELU) return false;
-    return (long)a.N * a.H * a.W >= (1L << 17);   // long row sets (the decoder token rows); short ones keep lin_rows (more, smaller workgroups)
-}
-static int launch_lin_stream(const ConvLaunch& a, hipStream_t stream) {
-    const long P = (long)a.N * a.H * a.W;
-    const int kc = a.src[0].C / 128;
-    const int rows_wg = kc > 1 ? 128 : 192;   // 4 waves x 2 or 3 row tiles
-    const long n_tasks = (P + rows_wg - 1) / rows_wg;
-    const unsigned grid = (unsigned)(n_tasks < 512 ? n_tasks : 512);   // two workgroups per CU
-    if (kc == 1)
-        hipLaunchKernelGGL(lin_stream_f16x3_kernel<1>, dim3(grid), dim3(256), 0, stream, a, n_tasks);
-    else if (kc == 2)
-        hipLaunchKernelGGL(lin_stream_f16x3_kernel<2>, dim3(grid), dim3(256), 0, stream, a, n_tasks);
-    else
-        hipLaunchKernelGGL(lin_stream_f16x3_kernel<3>, dim3(grid), dim3(256), 0, stream, a, n_tasks);
-    S3D_LAUNCH_CHECK();
-    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1288,9 +1245,7 @@ __global__ void conv_splitk_finish_kernel(const ConvLaunch a, int nsplit) {
 }
 
 int launch_conv_splitk_finish(const ConvLaunch& a, int nsplit, hipStream_t stream) {
-    const long total = (long)(((size_t)a.N * a.H * a.W * a.CoutPad) >> 2);
-    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(conv_splitk_finish_kernel, dim3(blocks), dim3(256), 0, stream, a, nsplit);
+    hipLaunchKernelGGL(conv_splitk_finish_kernel, dim3(conv_splitk_finish_blocks(a)), dim3(256), 0, stream, a, nsplit);
     S3D_LAUNCH_CHECK();
     return 0;
 }
@@ -1474,289 +1429,81 @@ __global__ __launch_bounds__(256) void conv3x3_small_f16x3_kernel(const ConvLaun
         if (pout[pt] >= 0) st4(part + (size_t)pout[pt] * a.CoutPad + jt * 16 + 4 * g, acc[pt]);
 }
 
-static bool conv3x3_lds_eligible(const ConvLaunch& a) {
-    if (a.ks != 3 || a.stride > 1 || (a.Hin && a.Hin != a.H) || (a.Win && a.Win != a.W)) return false;
-    if (!a.wpk16 || a.KU % 2 || a.CoutPad % 32) return false;
-    // maps smaller than the 8 x 16 tile waste lanes; they are worth it only when split-K supplies the parallelism
-    if ((a.W < 16 || a.H < 8) && !(a.splitk_ws && a.out_mode == S3D_OUT_NHWC)) return false;
-    for (int s = 0; s < a.nsrc; ++s)
-        if (a.src[s].C % 32 || a.src[s].sbcast) return false;
-    return true;
-}
-// Split count of a split-K launch of `nblk_k` workgroups per split over `nchunk` 32-channel chunks: the chip holds 512 of these
-// workgroups at a time (two per CU); a launch runs in ceil(workgroups / 512) rounds of (chunks per split + a fixed fetch /
-// epilogue share) each; the finish pass reads `se` partials.  Pick the count with the least rounds x length.
-static int conv_choose_splits(long nblk_k, int nchunk, size_t out_floats, size_t splitk_floats) {
-    int splits = 1;
-    long best = -1;
-    for (int sp = 1; sp <= nchunk && (size_t)sp * out_floats <= splitk_floats; ++sp) {
-        const int c = (nchunk + sp - 1) / sp, se = (nchunk + c - 1) / c;
-        if (se != sp) continue;   // (the same chunking as a smaller count)
-        const long rounds = (nblk_k * se + 511) / 512;
-        const long cost = rounds * (2 * c + 3) + (se > 1 ? 1 + se / 8 : 0);   // half-chunk units
-        if (best < 0 || cost < best) {
-            best = cost;
-            splits = se;
-        }
-    }
-    return splits;
-}
-static const bool g_conv_small_on = !(getenv("S3D_CONV_SMALL") && atoi(getenv("S3D_CONV_SMALL")) == 0);
-static const long g_conv_small_pmax = getenv("S3D_CONV_SMALL") && atoi(getenv("S3D_CONV_SMALL")) > 1 ? atoi(getenv("S3D_CONV_SMALL")) : 32;
+// ---------------------------------------------------------------------------------------------
+// launch_conv: plan (conv_plan.h — the one statement of which kernel serves what), then launch what the plan names.
+// The table below is every instantiation of the engine's kernels; a plan that names another one is an error.
+// ---------------------------------------------------------------------------------------------
+static_assert(kSmallHalo == C3S_HP && kSmallHalo1 == C3S_HP1, "conv_plan.h: pixels the small-map kernel parks");
+static const ConvTuning g_conv_tuning = conv_tuning_from_env();
+const ConvTuning& conv_tuning() { return g_conv_tuning; }
 
-// 1x1 convolutions of maps of a few pixels on conv3x3_small_f16x3_kernel<PT, false, 1> (split-K); false: not served
-static const bool g_conv_small1_on = !(getenv("S3D_CONV_SMALL_1X1") && atoi(getenv("S3D_CONV_SMALL_1X1")) == 0);
-// (up to 64 pixels — four pixel tiles: step 4.00-4.08 -> 3.96 ms with 32, 3.88 with 64; S3D_CONV_SMALL_1X1=0 / 32 for the A/B)
-static const long g_conv_small1_pmax = getenv("S3D_CONV_SMALL_1X1") && atoi(getenv("S3D_CONV_SMALL_1X1")) > 1 ? atoi(getenv("S3D_CONV_SMALL_1X1")) : 64;
-static bool conv1x1_small_eligible(const ConvLaunch& a) {
-    if (!g_conv_small1_on || a.ks != 1 || a.stride > 1 || a.Hin || a.Win || !a.wpk16 || a.KU % 2 || a.CoutPad % 64) return false;
-    if (!a.splitk_ws || a.out_mode != S3D_OUT_NHWC || a.gn.table) return false;
-    const long P = (long)a.N * a.H * a.W;
-    if (P > (g_conv_small1_pmax < 64 ? g_conv_small1_pmax : 64) || P > C3S_HP) return false;
-    for (int s = 0; s < a.nsrc; ++s)
-        if (a.src[s].C % 32 || a.src[s].sbcast) return false;
-    return true;
-}
-static int launch_conv1x1_small(const ConvLaunch& a, hipStream_t stream, bool& served) {
-    int nchunk = 0;
-    for (int s = 0; s < a.nsrc; ++s) nchunk += a.src[s].C >> 5;
-    const long P = (long)a.N * a.H * a.W;
-    int splits = conv_choose_splits(a.CoutPad / 64, nchunk, (size_t)P * a.CoutPad, a.splitk_floats);
-    const int cps = (nchunk + splits - 1) / splits;
-    splits = (nchunk + cps - 1) / cps;
-    served = splits > 1;
-    if (!served) return 0;
-    dim3 grid((unsigned)(a.CoutPad / 64), (unsigned)splits);
-    const int pt = (int)((P + 15) / 16);
-    if (pt == 1 && P <= C3S_HP1) hipLaunchKernelGGL((conv3x3_small_f16x3_kernel<1, false, 1>), grid, dim3(256), 0, stream, a, cps);
-    else if (pt <= 2) hipLaunchKernelGGL((conv3x3_small_f16x3_kernel<2, false, 1>), grid, dim3(256), 0, stream, a, cps);
-    else hipLaunchKernelGGL((conv3x3_small_f16x3_kernel<4, false, 1>), grid, dim3(256), 0, stream, a, cps);
-    S3D_LAUNCH_CHECK();
-    if (a.splits_out) {
-        *a.splits_out = splits;
-        return 0;
-    }
-    return launch_conv_splitk_finish(a, splits, stream);
-}
-
-static int launch_conv3x3_lds(const ConvLaunch& a, hipStream_t stream) {
-    const int tiles_x = (a.W + 15) / 16, tiles_y = (a.H + 7) / 8;
-    const long tiles = (long)tiles_x * tiles_y * a.N;
-    const int co_wg = a.CoutPad % 64 == 0 ? 64 : 32;
-    const long nblk = tiles * (a.CoutPad / co_wg);
-    S3D_CHECK_ARG(nblk < (1L << 31), "conv grid out of range (%ld)", nblk);
-    int nchunk = 0;
-    for (int s = 0; s < a.nsrc; ++s) nchunk += a.src[s].C >> 5;
-    // split-K when the pixel x channel tiling cannot fill the chip (deep encoder layers at batch 1)
-    int splits = 1;
-    const size_t out_floats = (size_t)a.N * a.H * a.W * a.CoutPad;
-    // maps of a few pixels (all images together at most 64 pixels, 160 with their zero borders): conv3x3_small_f16x3_kernel
-    const long P_all = (long)a.N * a.H * a.W;
-    // (P_all <= 32: at the 8 x 8 maps — four pixel tiles — this kernel measured 16.7-17.5 us per call against the tiled kernel's
-    //  16.1, in the compact form, in a conflict-free form over the zero-bordered index space and with the table loads ahead of
-    //  the weights; at the 4 x 4 maps 11.2 against 16.0: profiles/r06_ldm_small_maps.md.  S3D_CONV_SMALL=64 forces it there.)
-    const bool small = g_conv_small_on && a.splitk_ws && a.out_mode == S3D_OUT_NHWC && co_wg == 64 &&
-                       (P_all <= (g_conv_small_pmax < 64 ? g_conv_small_pmax : 64) || ((long)a.H * a.W <= 16 && P_all <= 64)) &&   // (four 4 x 4 images: 7.08 -> 7.01 ms per batch-4 step)
-                       (long)a.N * (a.H + 2) * (a.W + 2) <= C3S_HP;
-    const long nblk_k = small ? a.CoutPad / 64 : nblk;   // workgroups per split
-    if (a.splitk_ws && a.out_mode == S3D_OUT_NHWC && nblk_k < 512) splits = conv_choose_splits(nblk_k, nchunk, out_floats, a.splitk_floats);
-    // (doubling until 512 workgroups was the rule before round 4: it landed on 640 — two rounds, the second a quarter full — for
-    //  every 64 x 64 x 320 layer of the LDM U-Net)
-    const int cps = (nchunk + splits - 1) / splits;
-    splits = (nchunk + cps - 1) / cps;
-    if (small && splits > 1) {
-        dim3 sgrid((unsigned)(a.CoutPad / 64), (unsigned)splits);
-        const int pt = (int)((P_all + 15) / 16);
-        const long hp_all = (long)a.N * (a.H + 2) * (a.W + 2);
-#define C3S_LAUNCH(PT_)                                                                                                  \
-    if (a.gn.table) hipLaunchKernelGGL((conv3x3_small_f16x3_kernel<PT_, true>), sgrid, dim3(256), 0, stream, a, cps);      \
-    else hipLaunchKernelGGL((conv3x3_small_f16x3_kernel<PT_, false>), sgrid, dim3(256), 0, stream, a, cps)
-        if (pt == 1 && hp_all <= C3S_HP1) { C3S_LAUNCH(1); }
-        else if (pt <= 2) { C3S_LAUNCH(2); }
-        else { C3S_LAUNCH(4); }
-#undef C3S_LAUNCH
-        S3D_LAUNCH_CHECK();
-        if (a.splits_out) {
-            *a.splits_out = splits;
-            return 0;
-        }
-        return launch_conv_splitk_finish(a, splits, stream);
-    }
-    dim3 grid((unsigned)nblk, (unsigned)splits);
-    constexpr int one_buf_max = 2;   // chunks per workgroup up to which the single-buffer variant runs
-    const bool one = cps <= one_buf_max;   // 32-channel-output layers only: measured -13 % there, +5 % on the 64-wide tile
-    if (a.gn.table) {   // GroupNorm of the input in the staging path (LDM U-Net): its own instantiations (12 KiB of table)
-        int ct = 0;
-        for (int s = 0; s < a.nsrc; ++s) ct += a.src[s].C;
-        S3D_CHECK_ARG(ct <= S3D_GN_CMAX, "conv: fused GroupNorm over %d channels", ct);
-        if (co_wg == 64)
-            hipLaunchKernelGGL((conv3x3_lds_f16x3_kernel<4, 2, 2, 2, true>), grid, dim3(256), 0, stream, a, tiles_x, tiles_y, cps);
-        else
-            hipLaunchKernelGGL((conv3x3_lds_f16x3_kernel<2, 4, 1, 2, true>), grid, dim3(256), 0, stream, a, tiles_x, tiles_y, cps);
-    } else if (a.pre) {   // (launch_conv: no split-K workspace with an addend, so splits == 1)
-        if (co_wg == 64)
-            hipLaunchKernelGGL((conv3x3_lds_f16x3_kernel<4, 2, 2, 2, false, true>), grid, dim3(256), 0, stream, a, tiles_x, tiles_y, cps);
-        else
-            hipLaunchKernelGGL((conv3x3_lds_f16x3_kernel<2, 4, 1, 2, false, true>), grid, dim3(256), 0, stream, a, tiles_x, tiles_y, cps);
-    } else if (co_wg == 64) {
-        hipLaunchKernelGGL((conv3x3_lds_f16x3_kernel<4, 2, 2, 2>), grid, dim3(256), 0, stream, a, tiles_x, tiles_y, cps);
-    } else {
-        if (one) hipLaunchKernelGGL((conv3x3_lds_f16x3_kernel<2, 4, 1, 1>), grid, dim3(256), 0, stream, a, tiles_x, tiles_y, cps);
-        else hipLaunchKernelGGL((conv3x3_lds_f16x3_kernel<2, 4, 1, 2>), grid, dim3(256), 0, stream, a, tiles_x, tiles_y, cps);
-    }
-    S3D_LAUNCH_CHECK();
-    if (a.splits_out) {
-        *a.splits_out = splits;
-        if (splits > 1) return 0;   // the consumer sums the partials (and applies bias / residual) itself
-    }
-    if (splits > 1) return launch_conv_splitk_finish(a, splits, stream);
-    return 0;
-}
-
-// ConvLaunch::up2x.  Split precision (and single pass): conv_up2x_lds_f16x3_kernel, one launch.  fp32: the generic kernel, one
-// launch per output parity on that parity's rows of the weight image (correct, not tuned: no caller times it).
-static int launch_conv_up2x(const ConvLaunch& a, hipStream_t stream) {
-    if (!a.wpk16) {
-        const long P = (long)a.N * a.H * a.W;
-        const long nblk = ((P + 31) / 32) * (a.CoutPad / 32);
-        S3D_CHECK_ARG(nblk > 0 && nblk < (1L << 31), "conv grid out of range (%ld)", nblk);
-        for (int par = 0; par < 4; ++par) {
-            ConvLaunch b = a;
-            b.wpk = a.wpk + (size_t)par * (a.CoutPad / 16) * a.KU * 256;
-            b.out_py = par >> 1; b.out_px = par & 1;
-            b.tap_oy = b.out_py - 1; b.tap_ox = b.out_px - 1;
-            hipLaunchKernelGGL((conv_igemm_kernel<1, 1, 2, 2, 2, true, true>), dim3((unsigned)nblk), dim3(256), 0, stream, b);
-            S3D_LAUNCH_CHECK();
-        }
-        return 0;
-    }
-    const int tiles_x = (a.W + 15) / 16, tiles_y = (a.H + 7) / 8;
-    const long tiles = (long)tiles_x * tiles_y * a.N;
-#define UP_LAUNCH(MT_, WP_, WC_, NPY_, NPX_, NBUF_, OCC_)                                                                        \
-    do {                                                                                                                         \
-        const long nblk = tiles * (a.CoutPad / (WC_ * 32)) * (4 / (NPY_ * NPX_));                                                  \
-        S3D_CHECK_ARG(nblk < (1L << 31), "conv grid out of range (%ld)", nblk);                                                  \
-        hipLaunchKernelGGL((conv_up2x_lds_f16x3_kernel<MT_, WP_, WC_, NPY_, NPX_, NBUF_, OCC_>), dim3((unsigned)nblk), dim3(256), 0, \
-                           stream, a, tiles_x, tiles_y);                                                                         \
-    } while (0)
-    // One staged tile serves several parities (profiles/unet_upconv_composite.md): all four on the 32-channel tile (up4: 128 virtual
-    // output channels per workgroup; one LDS buffer, K is two chunks), the two of an output row on the 64-channel tile (up3: all of
-    // its 64 channels; up2: measured 152 us against 190 us with one parity per workgroup).  Both run two waves per SIMD without
-    // scratch.  The 32-channel tile fits the three waves of the plain 3x3 with ONE parity per workgroup only; that form measured
-    // 339-340 us at up4 against 275 us for this one (the two parities of a row: 318 us).
-    if (a.CoutPad % 64 == 0) UP_LAUNCH(4, 2, 2, 1, 2, 2, 2);
-    else UP_LAUNCH(2, 4, 1, 2, 2, 1, 2);
-#undef UP_LAUNCH
-    S3D_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int MT, int NT, int WM, int WN>
-static int launch_cfg(const ConvLaunch& a, hipStream_t stream) {
-    constexpr int PIX_WG = WM * MT * 16, CO_WG = WN * NT * 16;
-    const long P = (long)a.N * a.H * a.W;
-    const long nblk = ((P + PIX_WG - 1) / PIX_WG) * (a.CoutPad / CO_WG);
-    S3D_CHECK_ARG(nblk > 0 && nblk < (1L << 31), "conv grid out of range (%ld)", nblk);
-    dim3 grid((unsigned)nblk), block(WM * WN * 64);
-    bool f16 = a.wpk16 != nullptr && (a.KU % 2 == 0);
-    for (int s = 0; s < a.nsrc; ++s) f16 = f16 && (a.src[s].C % 32 == 0);
-    if (a.pre) {   // (launch_conv: 3x3 only)
-        if (f16) hipLaunchKernelGGL((conv_igemm_f16x3_kernel<MT, NT, WM, WN, 3, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((conv_igemm_kernel<MT, NT, WM, WN, 3, true>), grid, block, 0, stream, a);
-        S3D_LAUNCH_CHECK();
-        return 0;
-    }
-    if (f16) {
-        if (a.ks == 3)
-            hipLaunchKernelGGL((conv_igemm_f16x3_kernel<MT, NT, WM, WN, 3>), grid, block, 0, stream, a);
-        else if (a.ks == 2)
-            hipLaunchKernelGGL((conv_igemm_f16x3_kernel<MT, NT, WM, WN, 2>), grid, block, 0, stream, a);
-        else
-            hipLaunchKernelGGL((conv_igemm_f16x3_kernel<MT, NT, WM, WN, 1>), grid, block, 0, stream, a);
-        S3D_LAUNCH_CHECK();
-        return 0;
-    }
-    if (a.ks == 3)
-        hipLaunchKernelGGL((conv_igemm_kernel<MT, NT, WM, WN, 3>), grid, block, 0, stream, a);
-    else if (a.ks == 2)
-        hipLaunchKernelGGL((conv_igemm_kernel<MT, NT, WM, WN, 2>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL((conv_igemm_kernel<MT, NT, WM, WN, 1>), grid, block, 0, stream, a);
-    S3D_LAUNCH_CHECK();
-    return 0;
-}
+struct ConvKernel {
+    ConvFamily family;
+    int targ[7];
+    void (*launch)(const ConvLaunch& a, const ConvPlan& p, hipStream_t stream);
+};
+#define CK_ARGS(...) __VA_ARGS__
+#define CK(FAMILY, KERNEL, ARGS, ...)                                                                                       \
+    {FAMILY, {__VA_ARGS__}, [](const ConvLaunch& a, const ConvPlan& p, hipStream_t stream) {                                 \
+         hipLaunchKernelGGL((KERNEL<__VA_ARGS__>), dim3(p.grid_x, p.grid_y), dim3(p.block), 0, stream, CK_ARGS ARGS);        \
+     }}
+#define CK_TILE(...)   /* one tile of the menu: fp32 and split precision, ks 1 / 2 / 3 and 3 with an addend */                \
+    CK(CONV_IGEMM, conv_igemm_kernel, (a), __VA_ARGS__, 1, 0, 0), CK(CONV_IGEMM, conv_igemm_kernel, (a), __VA_ARGS__, 2, 0, 0),       \
+    CK(CONV_IGEMM, conv_igemm_kernel, (a), __VA_ARGS__, 3, 0, 0), CK(CONV_IGEMM, conv_igemm_kernel, (a), __VA_ARGS__, 3, 1, 0),       \
+    CK(CONV_IGEMM_F16X3, conv_igemm_f16x3_kernel, (a), __VA_ARGS__, 1, 0), CK(CONV_IGEMM_F16X3, conv_igemm_f16x3_kernel, (a), __VA_ARGS__, 2, 0), \
+    CK(CONV_IGEMM_F16X3, conv_igemm_f16x3_kernel, (a), __VA_ARGS__, 3, 0), CK(CONV_IGEMM_F16X3, conv_igemm_f16x3_kernel, (a), __VA_ARGS__, 3, 1)
+#define CK_LDS(...) CK(CONV_LDS, conv3x3_lds_f16x3_kernel, (a, p.tiles_x, p.tiles_y, p.chunks_per_split), __VA_ARGS__)
+#define CK_SMALL(...) CK(CONV_SMALL, conv3x3_small_f16x3_kernel, (a, p.chunks_per_split), __VA_ARGS__)
+#define CK_UP2X(...) CK(CONV_UP2X_LDS, conv_up2x_lds_f16x3_kernel, (a, p.tiles_x, p.tiles_y), __VA_ARGS__)
+#define CK_STREAM(KC) CK(CONV_LIN_STREAM, lin_stream_f16x3_kernel, (a, p.n_tasks), KC)
+static const ConvKernel kConvKernels[] = {
+    CK_TILE(4, 4, 2, 2), CK_TILE(2, 4, 2, 2), CK_TILE(1, 4, 2, 2), CK_TILE(1, 1, 2, 2), CK_TILE(4, 4, 4, 1), CK_TILE(2, 2, 2, 2),
+    CK_TILE(4, 2, 4, 1), CK_TILE(4, 1, 4, 1), CK_TILE(1, 1, 4, 1),
+    CK(CONV_IGEMM, conv_igemm_kernel, (a), 1, 1, 2, 2, 2, 1, 1),   // fp32 up2x, one launch per output parity
+    // MT, WP, WC, NBUF, GN, PRE
+    CK_LDS(4, 2, 2, 2, 0, 0), CK_LDS(4, 2, 2, 2, 1, 0), CK_LDS(4, 2, 2, 2, 0, 1),
+    CK_LDS(2, 4, 1, 2, 0, 0), CK_LDS(2, 4, 1, 2, 1, 0), CK_LDS(2, 4, 1, 2, 0, 1), CK_LDS(2, 4, 1, 1, 0, 0),
+    // PT, GN, TAPS
+    CK_SMALL(1, 0, 9), CK_SMALL(2, 0, 9), CK_SMALL(4, 0, 9), CK_SMALL(1, 1, 9), CK_SMALL(2, 1, 9), CK_SMALL(4, 1, 9),
+    CK_SMALL(1, 0, 1), CK_SMALL(2, 0, 1), CK_SMALL(4, 0, 1),
+    // MT, WP, WC, NPY, NPX, NBUF, OCC
+    CK_UP2X(4, 2, 2, 1, 2, 2, 2), CK_UP2X(2, 4, 1, 2, 2, 1, 2),
+    CK_STREAM(1), CK_STREAM(2), CK_STREAM(3),
+    {CONV_LIN_ROWS, {}, [](const ConvLaunch& a, const ConvPlan& p, hipStream_t stream) {
+         hipLaunchKernelGGL(lin_rows_f16x3_kernel, dim3(p.grid_x), dim3(p.block), 0, stream, a);
+     }}};
 
 int launch_conv(const ConvLaunch& a_in, hipStream_t stream) {
     ConvLaunch a = a_in;
     a.xcd_remap = 1;   // block -> (pixel tile, cout tile) mapping keeps the cout tiles of a pixel tile on one XCD
-    S3D_CHECK_ARG(a.ks >= 1 && a.ks <= 3, "conv: ks must be 1, 2 or 3");
-    S3D_CHECK_ARG(!a.pad_origin || (a.ks == 3 && a.stride > 1 && a.out_mode == S3D_OUT_NHWC),
-                  "conv: pad_origin is served for strided 3x3 convolutions only");
-    S3D_CHECK_ARG(a.CoutPad % 16 == 0 && a.CoutPad > 0, "conv: CoutPad %d", a.CoutPad);
-    for (int s = 0; s < a.nsrc; ++s)
-        S3D_CHECK_ARG(a.src[s].C % 16 == 0 && a.src[s].bdiv >= 1, "conv: bad source %d", s);
-    // ConvTranspose output: the quadrant-scatter store carries affine + activation only.  Its full-line form (32-channel
-    // pairs, conv_epilogue) pairs accumulator tiles (jt0 + 2 np, jt0 + 2 np + 1) with jt0 = a multiple of NT — even for
-    // every tile shape of the menu below — and would index dropout / gate / residual by the SCATTERED offset.
-    S3D_CHECK_ARG(a.out_mode != S3D_OUT_CONVT || (a.drop.p <= 0.f && !a.gate && !a.residual && !a.out_accumulate),
-                  "conv: ConvTranspose output takes no dropout / gate / residual / accumulate");
-    // A pre-activation addend is the accumulators' starting value in the 3x3 kernels.  Not served: the ConvTranspose scatter,
-    // split-K (every split would start at it; the small-map kernels run on split-K only), the 1x1 row-linear kernels, a fused
-    // GroupNorm instantiation
-    S3D_CHECK_ARG(!a.pre || a.up2x || (a.ks == 3 && a.stride <= 1 && !a.Hin && !a.Win), "conv: a pre-activation addend is served for 3x3 stride-1 convolutions only");
-    S3D_CHECK_ARG(!a.pre || a.out_mode != S3D_OUT_CONVT, "conv: a pre-activation addend with a ConvTranspose output");
-    S3D_CHECK_ARG(!a.pre || !a.splitk_ws, "conv: a pre-activation addend with a split-K workspace");
-    S3D_CHECK_ARG(!a.pre || !a.gn.table, "conv: a pre-activation addend with a fused GroupNorm");
-    S3D_CHECK_ARG(!a.pre || (a.pre_bdiv >= 1 && a.pre_bmod >= 0), "conv: addend image rule bdiv %d bmod %d", a.pre_bdiv, a.pre_bmod);
-    // The composed ConvTranspose -> 3x3 is its own 2x2 form on the low-resolution grid with its own kernels.  Not served with it:
-    // split-K, a fused GroupNorm, the ConvTranspose scatter or NCHW, a second or broadcast source, any epilogue beyond scale / shift / ReLU
-    if (a.up2x) {
-        S3D_CHECK_ARG(a.ks == 2 && a.stride <= 1 && !a.Hin && !a.Win, "conv: the composed ConvTranspose -> 3x3 is a 2x2 stride-1 form (ks %d)", a.ks);
-        S3D_CHECK_ARG(!a.splitk_ws && !a.splits_out, "conv: the composed ConvTranspose -> 3x3 with a split-K workspace");
-        S3D_CHECK_ARG(!a.gn.table, "conv: the composed ConvTranspose -> 3x3 with a fused GroupNorm");
-        S3D_CHECK_ARG(a.out_mode == S3D_OUT_NHWC && a.cout_store == a.CoutPad, "conv: the composed ConvTranspose -> 3x3 stores NHWC, all channels");
-        S3D_CHECK_ARG(a.pre && a.pre_tab, "conv: the composed ConvTranspose -> 3x3 needs its addend and its border-class table");
-        S3D_CHECK_ARG(a.nsrc == 1 && !a.src[0].sbcast && a.src[0].C % 32 == 0 && a.CoutPad % 32 == 0 && a.KU == a.src[0].C / 4,
-                      "conv: the composed ConvTranspose -> 3x3 takes one plain source (C %d, Cout %d, KU %d)", a.src[0].C, a.CoutPad, a.KU);
-        S3D_CHECK_ARG(!a.pad_origin && a.out_cstride >= a.CoutPad && a.src[0].bdiv >= 1 && a.src[0].bmod >= 0 && a.pre_bdiv >= 1 && a.pre_bmod >= 0,
-                      "conv: the composed ConvTranspose -> 3x3: pad_origin %d, channel stride %d < %d, or a bad image rule", a.pad_origin, a.out_cstride, a.CoutPad);
-        S3D_CHECK_ARG(a.drop.p <= 0.f && !a.gate && !a.residual && !a.out_accumulate && (a.act == S3D_ACT_NONE || a.act == S3D_ACT_RELU),
-                      "conv: the composed ConvTranspose -> 3x3 takes scale / shift / ReLU only");
-        return launch_conv_up2x(a, stream);
+    const ConvPlan p = conv_plan(a, g_conv_tuning);
+    if (p.err) return p.err;
+    const ConvKernel* k = nullptr;
+    for (const ConvKernel& e : kConvKernels)
+        if (e.family == p.family && std::equal(e.targ, e.targ + 7, p.targ)) {
+            k = &e;
+            break;
+        }
+    S3D_CHECK_ARG(k, "conv: the plan names a kernel instantiation that is not built");
+    for (int par = 0; par < (p.per_parity ? 4 : 1); ++par) {
+        if (p.per_parity) {   // that parity's rows of the weight image, its taps and its output pixels
+            a.wpk = a_in.wpk + (size_t)par * (a.CoutPad / 16) * a.KU * 256;
+            a.out_py = par >> 1; a.out_px = par & 1;
+            a.tap_oy = a.out_py - 1; a.tap_ox = a.out_px - 1;
+        }
+        k->launch(a, p, stream);
+        S3D_LAUNCH_CHECK();
     }
-    S3D_CHECK_ARG(!a.pre_tab, "conv: a border-class table without the composed ConvTranspose -> 3x3");
-    if (conv3x3_lds_eligible(a)) return launch_conv3x3_lds(a, stream);
-    S3D_CHECK_ARG(!a.gn.table, "conv: a fused GroupNorm needs the LDS-staged 3x3 kernel (ks 3, stride 1, channel counts multiples of 32)");
-    if (conv1x1_small_eligible(a)) {
-        bool served = false;
-        const int rc = launch_conv1x1_small(a, stream, served);
-        if (rc || served) return rc;
-    }
-    if (lin_stream_eligible(a)) return launch_lin_stream(a, stream);
-    if (lin_rows_eligible(a)) return launch_lin_rows(a, stream);
-    const long P = (long)a.N * a.H * a.W;
-    // Tile menu: (pixels x couts) per workgroup of 4 waves.  Prefer the largest tile that still
-    // yields >= ~2 workgroups per CU; small late-encoder maps fall through to the small tiles.
-    const long want = 512;
-    auto nblk = [&](int pix, int co) { return ((P + pix - 1) / pix) * (a.CoutPad / co); };
-    if (a.CoutPad % 128 == 0) {
-        if (nblk(128, 128) >= want) return launch_cfg<4, 4, 2, 2>(a, stream);
-        if (nblk(64, 128) >= want) return launch_cfg<2, 4, 2, 2>(a, stream);
-        if (a.CoutPad % 128 == 0 && nblk(32, 128) >= want / 2) return launch_cfg<1, 4, 2, 2>(a, stream);
-        return launch_cfg<1, 1, 2, 2>(a, stream);  // 32 px x 32 co
-    }
-    if (a.CoutPad % 64 == 0) {
-        if (nblk(256, 64) >= want) return launch_cfg<4, 4, 4, 1>(a, stream);
-        if (nblk(64, 64) >= want / 2) return launch_cfg<2, 2, 2, 2>(a, stream);
-        return launch_cfg<1, 1, 2, 2>(a, stream);
-    }
-    if (a.CoutPad % 32 == 0) {
-        if (nblk(256, 32) >= want) return launch_cfg<4, 2, 4, 1>(a, stream);
-        return launch_cfg<1, 1, 2, 2>(a, stream);
-    }
-    if (nblk(256, 16) >= want) return launch_cfg<4, 1, 4, 1>(a, stream);
-    return launch_cfg<1, 1, 4, 1>(a, stream);
+    if (a.splits_out) *a.splits_out = p.splits;   // > 1: the consumer sums the partials (and applies bias / residual) itself
+    return p.finish ? launch_conv_splitk_finish(a, p.splits, stream) : 0;
 }
+#undef CK_ARGS
+#undef CK
+#undef CK_TILE
+#undef CK_LDS
+#undef CK_SMALL
+#undef CK_UP2X
+#undef CK_STREAM
 
 // ---------------------------------------------------------------------------------------------
 // packers

@@ -318,7 +318,7 @@ def test_conv_gn_fwd_matches_fp64(case):
 # -------------------------------------------------------------------------------------------------------- s3d_conv_strided_fwd
 # (id, N, Hin, Win, cin, cout, ks, stride, pad_origin)
 STRIDED_CASES = [
-    ("strided_f16x3_4_1_4_1-ks3-s2-origin", 2, 15, 9, 64, 48, 3, 2, 1),
+    ("strided_f16x3_1_1_4_1-ks3-s2-origin", 2, 15, 9, 64, 48, 3, 2, 1),
     ("strided_fp32-cin3-ks3-s2", 3, 17, 13, 3, 36, 3, 2, 0),
     ("strided_f16x3_1_1_2_2-ks3-s2", 2, 33, 21, 32, 124, 3, 2, 0),
     ("strided_f16x3-ks1-s2", 2, 19, 23, 128, 100, 1, 2, 0),
