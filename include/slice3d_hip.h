@@ -29,9 +29,10 @@
 extern "C" {
 #endif
 
-#define S3D_VERSION 123          /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding; 119: s3d_mesh_render_*; 120: s3d_unet_encode_fwd computes the decoder's slice-invariant terms once per image, the weights-only ones in s3d_unet_pack (other packed-image and workspace sizes: query them); 121: up2-up4 run ConvTranspose and the first 3x3's up half as one convolution of the low-resolution map with weights composed in s3d_unet_pack (packed-image and workspace sizes change again); 122: s3d_mesh_simplify_*; 123: s3d_conv_plan_describe */
+#define S3D_VERSION 124         /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding; 119: s3d_mesh_render_*; 120: s3d_unet_encode_fwd computes the decoder's slice-invariant terms once per image, the weights-only ones in s3d_unet_pack (other packed-image and workspace sizes: query them); 121: up2-up4 run ConvTranspose and the first 3x3's up half as one convolution of the low-resolution map with weights composed in s3d_unet_pack (packed-image and workspace sizes change again); 122: s3d_mesh_simplify_*; 123: s3d_conv_plan_describe; 124: s3d_mesh_topology_* */
 #define S3D_E_ARG (-1)           /* bad argument / unsupported shape */
 #define S3D_E_WORKSPACE (-2)     /* workspace or packed-weight buffer too small */
+#define S3D_E_ROUNDS (-3)        /* s3d_mesh_topology_run: the component labels did not converge within its round bound */
 
 #define S3D_N_LEVELS 5           /* feature pyramid levels, coarse -> fine (unet_custom.py:58-67) */
 #define S3D_D_MODEL 128
@@ -758,6 +759,56 @@ int s3d_mesh_simplify_run(const double* vertices, long n_vertices, const long lo
                           long* n_vertices_out, long* n_faces_out, int* n_rounds, void* stream);
 int s3d_mesh_simplify_emit(const void* workspace, size_t workspace_bytes, long n_vertices, long n_faces,
                            double* vertices_out, long long* faces_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh topology (mesh_topology.hip; slice3d_amd/mesh_topology.py, reg_slices/clean_meshes.py): weld of equal positions,
+ * connected components, per-component counts and measures, order-preserving removal of components.  Mesh conventions
+ * as above.  `weld` (0 / 1) is part of the workspace's layout: pass the same value to every call on one workspace.
+ *
+ * Weld: two vertices that faces reference are one when their three coordinates compare equal as doubles (-0.0 equals
+ * +0.0, 1 ulp apart does not); the class's representative is its smallest index; vmap[v] = the representative, v itself
+ * for a vertex no face references.  Everything below works on vmap[faces].  Without weld vmap is the identity.
+ * Components: two faces are connected when they share a welded vertex (a face that repeats an index still connects its
+ * vertices); ids 0..K-1 in ascending order of the component's smallest welded vertex index.  Labels only decrease
+ * (integer atomicMin); a round is hook, pointer jumping and a re-check of every face in three launches and one stream
+ * synchronisation; at most 64 rounds, else S3D_E_ROUNDS.  A stale read of a label may cost a round (n_rounds is the one
+ * output that may differ between two runs), never a label.
+ * Table: K rows and a summary row over all faces.  counts (K + 1, 11) int64: faces, referenced welded vertices,
+ * undirected edges, edges with one / two / three or more half-edges, directed edges that occur more than once,
+ * faces that repeat an index, V - E + F, closed_oriented (every edge twice, every directed edge once), oriented_with_border
+ * (every edge once or twice, every directed edge once).  measures (K + 1, 8) float64: area, signed volume (sum of
+ * det(v0, v1, v2) / 6), bounding box lo xyz, hi xyz.  A float64 sum runs over the row's faces in ascending face index, in
+ * blocks of 256 whose sums are added in ascending order: the same bits from run to run.
+ *   run:         validates the indices with a kernel of its own before anything dereferences them.  S3D_E_ARG with a
+ *                message for an index outside [0, n_vertices), with weld for a referenced vertex with a coordinate that is
+ *                not finite (an unreferenced one is ignored), for a workspace below s3d_mesh_topology_workspace_bytes.
+ *                n_faces == 0 gives 0 components.  summary_host (optional, HOST, 11 int64): the summary row's counts.
+ *   emit_labels: vmap[V], face_component[F], vertex_component[V] (-1 for a vertex no face references); int64, each optional.
+ *   emit_table:  counts and measures as above, n_components as run returned it.
+ *   keep_run:    keep[K] (uint8, device) selects components; drop_degenerate also drops the faces that repeat a welded index.
+ *                Returns the sizes of the kept mesh through one stream synchronisation.
+ *   keep_emit:   the kept faces in ascending original face index, the vertices they reference in ascending original index
+ *                (with weld, the representative's), indices remapped: the convention of s3d_mesh_simplify_emit.
+ *                `vertices` is the input array of run.
+ * The last launch of run writes K, the sizes and weld into the workspace's header.  Every emit and keep call reads it back
+ * (one stream synchronisation) before anything else and returns S3D_E_ARG when no run has completed on the workspace, when
+ * n_vertices, n_faces or weld are not that run's, when n_components is not the K it found, or (keep_emit) when no keep_run
+ * has completed since.  keep must hold n_components flags.
+ * workspace_bytes returns 0 for sizes it cannot serve (n_faces < 0 or >= 2^29, n_vertices < 0 or >= 2^30).
+ * ------------------------------------------------------------------------------------------- */
+size_t s3d_mesh_topology_workspace_bytes(long n_vertices, long n_faces, int weld);
+int s3d_mesh_topology_run(const double* vertices, long n_vertices, const long long* faces, long n_faces, int weld,
+                          void* workspace, size_t workspace_bytes, long* n_components, int* n_rounds,
+                          long long* summary_host, void* stream);
+int s3d_mesh_topology_emit_labels(const void* workspace, size_t workspace_bytes, long n_vertices, long n_faces, int weld,
+                                  long long* vmap, long long* face_component, long long* vertex_component, void* stream);
+int s3d_mesh_topology_emit_table(const void* workspace, size_t workspace_bytes, long n_vertices, long n_faces, int weld,
+                                 long n_components, long long* counts, double* measures, void* stream);
+int s3d_mesh_topology_keep_run(void* workspace, size_t workspace_bytes, long n_vertices, long n_faces, int weld,
+                               long n_components, const unsigned char* keep, int drop_degenerate, long* n_vertices_out,
+                               long* n_faces_out, void* stream);
+int s3d_mesh_topology_keep_emit(const void* workspace, size_t workspace_bytes, const double* vertices, long n_vertices,
+                                long n_faces, int weld, double* vertices_out, long long* faces_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Dataset staging on the device — the per-sample tensor work of Slice3DDataset.__getitem__

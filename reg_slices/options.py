@@ -75,6 +75,13 @@ _BUILD_FLAGS = [
     ("simplify_nfaces", dict(type=int, default=None, help="[build] reconstruct.py: simplify every mesh to about this many "
                                                          "faces on the GPU before export (slice3d_amd/mesh_simplify.py, "
                                                          "the reference's Generator3D(simplify_nfaces=...))")),
+    ("keep_largest", dict(type=int, default=None, help="[build] reconstruct.py: keep only this many of the extracted mesh's "
+                                                       "largest connected components (slice3d_amd/mesh_topology.py), "
+                                                       "before --simplify_nfaces")),
+    ("min_component_frac", dict(type=float, default=0.0, help="[build] reconstruct.py: drop the components below this share "
+                                                              "of the largest one in --component_measure")),
+    ("component_measure", dict(type=str, default="faces", choices=["faces", "area", "volume"],
+                               help="[build] what --keep_largest and --min_component_frac rank components by")),
 ]
 
 

@@ -3,7 +3,8 @@ load a checkpoint into Slices3DRegModel(mode='test'), run Generator3D (MISE or d
 -> marching cubes) per test object and export `<shape>.obj`, with the reference's flags.
 
     python reg_slices/reconstruct.py --name_exp demo --name_ckpt x.ckpt --name_dataset synthetic \
-        --mode test --img_size 128 --mc_res0 64 --mc_up_steps 2 [--simplify_nfaces 10000]
+        --mode test --img_size 128 --mc_res0 64 --mc_up_steps 2 [--keep_largest 1] [--min_component_frac 0.01] \
+        [--component_measure faces|area|volume] [--simplify_nfaces 10000]
 
 With --name_model gtslice --from_which_slices gen --gen_ckpt <LatentDiffusion .ckpt> the slices are generated in memory
 (slice3d_amd/gen_route.py): per batch of --n_bs test objects, input view 004 -> SliceDiffusion.generate -> the 8-bit mosaic
@@ -28,7 +29,19 @@ from slice3d_amd.synth import SyntheticSlice3DDataset  # noqa: E402
 
 def export_mesh(args, mesh, stats, path_mesh):
     """--simplify_nfaces N: simplify_mesh(mesh, N, 5.) as the reference's Generator3D.extract_mesh does (reconstruct.py:231-235
-    there), on the GPU; then `<shape>.obj`."""
+    there), on the GPU; then `<shape>.obj`.  --keep_largest K / --min_component_frac f (ranked by --component_measure) first
+    drop the small detached components marching cubes emits (slice3d_amd/mesh_topology.py), so that they neither reach the
+    file nor eat the simplifier's face budget."""
+    if (args.keep_largest is not None or args.min_component_frac > 0.0) and len(mesh.faces):
+        from slice3d_amd.mesh_topology import keep_components, mesh_topology, select_components
+        torch.cuda.synchronize()
+        t0 = time.time()
+        topo = mesh_topology(mesh)
+        mask = select_components(topo.table, largest=args.keep_largest, by=args.component_measure,
+                                 min_frac=args.min_component_frac)
+        mesh = keep_components(mesh, mask, topology=topo)
+        stats["components (in / kept)"] = "%d / %d" % (topo.n_components, int(mask.sum()))
+        stats["time (clean)"] = time.time() - t0
     if args.simplify_nfaces is not None and len(mesh.faces):
         from slice3d_amd.mesh_simplify import simplify_mesh
         torch.cuda.synchronize()

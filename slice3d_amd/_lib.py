@@ -220,6 +220,13 @@ SYMBOLS = {
     "s3d_mesh_simplify_run": (_i, [_vp, _l, _vp, _l, _l, C.c_double, _vp, _sz, C.POINTER(C.c_long), C.POINTER(C.c_long),
                                    C.POINTER(C.c_int), _vp]),
     "s3d_mesh_simplify_emit": (_i, [_vp, _sz, _l, _l, _vp, _vp, _vp]),
+    "s3d_mesh_topology_workspace_bytes": (_sz, [_l, _l, _i]),
+    "s3d_mesh_topology_run": (_i, [_vp, _l, _vp, _l, _i, _vp, _sz, C.POINTER(C.c_long), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_longlong), _vp]),
+    "s3d_mesh_topology_emit_labels": (_i, [_vp, _sz, _l, _l, _i, _vp, _vp, _vp, _vp]),
+    "s3d_mesh_topology_emit_table": (_i, [_vp, _sz, _l, _l, _i, _l, _vp, _vp, _vp]),
+    "s3d_mesh_topology_keep_run": (_i, [_vp, _sz, _l, _l, _i, _l, _vp, _i, C.POINTER(C.c_long), C.POINTER(C.c_long), _vp]),
+    "s3d_mesh_topology_keep_emit": (_i, [_vp, _sz, _vp, _l, _l, _i, _vp, _vp, _vp]),
     "s3d_dataset_images_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "s3d_dataset_points_fwd": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _vp]),
     "s3d_nchw_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
