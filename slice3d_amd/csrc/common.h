@@ -67,8 +67,17 @@ void s3d_set_error(const char* fmt, ...);
             return (int)e__;                                          \
         }                                                             \
     } while (0)
+// a HIP runtime call of the entry point `what`: on failure "what: <hip error>" and the hipError_t as the return value
+#define S3D_HIP_TRY(what, expr)                                       \
+    do {                                                              \
+        const hipError_t e__ = (expr);                                \
+        if (e__ != hipSuccess) {                                      \
+            s3d_set_error("%s: %s", what, hipGetErrorString(e__));    \
+            return (int)e__;                                          \
+        }                                                             \
+    } while (0)
 
-#define TRY_RET(x)               \
+#define TRY_RET(x)             \
     do {                         \
         int rc__ = (x);          \
         if (rc__) return rc__;   \

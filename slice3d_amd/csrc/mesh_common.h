@@ -1,7 +1,14 @@
-// mesh_common.h — what the mesh translation units (mesh_eval.hip, mesh_sdf.hip) share: the workspace alignment, the
-// deterministic tiled scan and the partial bounding boxes over the vertices that the faces reference.
+// mesh_common.h — what the mesh translation units (mesh_eval.hip, mesh_sdf.hip, mesh_render.hip, mesh_simplify.hip,
+// mesh_topology.hip) share, and what a new one starts from.  Host scaffolding: the workspace arena (MeArena), the 1-D
+// launch (me_blocks, ME_LAUNCH; S3D_HIP_TRY is common.h's) and the tail of a cell-list build (me_lists_finish).  Device
+// code: the deterministic tiled scan (me_scan, me_scan_total), the partial bounding boxes over the vertices that the
+// faces reference and their fold (me_bbox_partial_kernel, me_bbox_fold), the float64 3-vectors (me_v3) and the emit of
+// the vertices a compaction keeps (me_emit_vertices_kernel).  The algorithms (which cells a face goes to, which lists a
+// vertex has) stay with their units.
 #pragma once
 #include <math.h>
+
+#include <algorithm>
 
 #include "common.h"
 
@@ -12,6 +19,24 @@
 #define ME_RES_MAX 8192                     // hash_resolution bound: res^2 cells in 32-bit indexing
 
 static inline size_t me_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// carves a caller's workspace into 256-byte aligned arrays, in the order of the take calls; with base == nullptr it only
+// adds up the bytes.  A unit's layout function is one pass of takes into its struct and returns `off`, so an array's
+// size is written once.
+struct MeArena {
+    char* base;
+    size_t off = 0;
+    template <typename T>
+    T* take(size_t n) {
+        const size_t at = off;
+        off += me_align(n * sizeof(T));
+        return base ? (T*)(base + at) : nullptr;
+    }
+};
+
+// 1-D launch of ME_BLOCK threads over n items.  The grid is at least one block; for n >= 1 that is ceil(n / ME_BLOCK).
+static inline unsigned me_blocks(long n) { return (unsigned)std::max<long>(1, (n + ME_BLOCK - 1) / ME_BLOCK); }
+#define ME_LAUNCH(kernel, n, st, ...) hipLaunchKernelGGL(kernel, dim3(me_blocks(n)), dim3(ME_BLOCK), 0, st, __VA_ARGS__)
 
 // =============================================================================================
 // tiled scan of n items (exclusive for counts -> offsets, inclusive for areas -> cdf); deterministic order
@@ -96,6 +121,32 @@ static void me_scan(const Tin* in, T* out, long n, T* tsum, hipStream_t st) {
     hipLaunchKernelGGL((me_scan_totals_kernel<T>), dim3(1), dim3(ME_BLOCK), 0, st, tsum, tiles);
     hipLaunchKernelGGL((me_add_tile_offsets_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, n, tsum);
 }
+// where me_scan leaves the grand total of its n items: behind the tile totals, at tsum[tiles] (tsum holds tiles + 1).
+// An exclusive scan over n + 1 items also leaves the total of the first n in out[n]: the simplifier's vertex count and
+// the topology's K are read there.
+template <typename T>
+static inline T* me_scan_total(T* tsum, long n) {
+    return tsum + (n + ME_TILE - 1) / ME_TILE;
+}
+
+// The tail of a cell-list build (the cells of a hash or grid, the tiles of an image): cnt[0 .. n) -> off[0 .. n], the
+// exclusive scan with the grand total behind the last offset; the total and flags[0] come back to the host with the
+// build's one stream synchronisation.  flags[0] is what me_bbox_partial_kernel raises.
+static int me_lists_finish(const char* what, const unsigned* cnt, long long* off, long n, long long* tsum, const int* flags,
+                           long n_vertices, long* n_entries, hipStream_t st) {
+    me_scan<unsigned, long long, false>(cnt, off, n, tsum, st);
+    S3D_LAUNCH_CHECK();
+    long long total = 0;
+    int bad = 0;
+    // the scan writes off[0 .. n); the end of the last list is the grand total
+    S3D_HIP_TRY(what, hipMemcpyAsync(off + n, me_scan_total(tsum, n), 8, hipMemcpyDeviceToDevice, st));
+    S3D_HIP_TRY(what, hipMemcpyAsync(&total, me_scan_total(tsum, n), 8, hipMemcpyDeviceToHost, st));
+    S3D_HIP_TRY(what, hipMemcpyAsync(&bad, flags, 4, hipMemcpyDeviceToHost, st));
+    S3D_HIP_TRY(what, hipStreamSynchronize(st));
+    S3D_CHECK_ARG(!bad, "%s: a face indexes a vertex outside [0, %ld)", what, n_vertices);
+    *n_entries = (long)total;
+    return 0;
+}
 
 // bbox over the vertices the faces reference (inside_mesh.py:12-15 takes it over mesh.vertices[mesh.faces])
 static __global__ __launch_bounds__(ME_BLOCK) void me_bbox_partial_kernel(const double* __restrict__ verts, long nv,
@@ -133,4 +184,37 @@ static __global__ __launch_bounds__(ME_BLOCK) void me_bbox_partial_kernel(const 
         __syncthreads();
     }
     if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = s[threadIdx.x][0];
+}
+// the fold of the nb partial boxes in block order (one thread's work): lo / hi stay +inf / -inf without a valid face
+__device__ __forceinline__ void me_bbox_fold(const double* __restrict__ part, int nb, double* lo, double* hi) {
+    for (int a = 0; a < 3; ++a) lo[a] = INFINITY, hi[a] = -INFINITY;
+    for (int b = 0; b < nb; ++b)
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = fmin(lo[a], part[6 * b + a]);
+            hi[a] = fmax(hi[a], part[6 * b + 3 + a]);
+        }
+}
+
+// =============================================================================================
+// float64 3-vectors; every product and sum is rounded on its own (the mesh units are compiled with -ffp-contract=off)
+// =============================================================================================
+struct me_v3 {
+    double x, y, z;
+};
+static __device__ __forceinline__ me_v3 me_ld(const double* __restrict__ P, int v) {
+    return me_v3{P[3 * (long)v], P[3 * (long)v + 1], P[3 * (long)v + 2]};
+}
+static __device__ __forceinline__ me_v3 me_sub(me_v3 a, me_v3 b) { return me_v3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+static __device__ __forceinline__ double me_dot(me_v3 a, me_v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+static __device__ __forceinline__ me_v3 me_cross(me_v3 a, me_v3 b) {
+    return me_v3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+
+// out[vmap[v]] = P[v] for the vertices a compaction keeps (used[v]); vmap is the exclusive scan of used
+static __global__ void me_emit_vertices_kernel(const double* __restrict__ P, const int* __restrict__ used,
+                                               const int* __restrict__ vmap, long nv, double* __restrict__ out) {
+    const long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv || !used[v]) return;
+    const long d = vmap[v];
+    out[3 * d] = P[3 * v], out[3 * d + 1] = P[3 * v + 1], out[3 * d + 2] = P[3 * v + 2];
 }

@@ -28,42 +28,25 @@ struct ContainsWs {
     unsigned* cnt;         // [res*res] triangles per cell, then the fill cursors
     long long* off;        // [res*res + 1] first entry of each cell
     long long* tsum;       // [tiles + 1]
-    long cells, tiles;
+    long cells;
 };
-static size_t contains_layout(long nf, int res, ContainsWs* w, char* base) {
-    const long cells = (long)res * res, tiles = (cells + ME_TILE - 1) / ME_TILE;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += me_align(bytes);
-        return o;
-    };
-    const size_t o_part = take(ME_BBOX_BLOCKS * 6 * 8), o_prm = take(8 * 8), o_flags = take(16), o_tri = take((size_t)nf * 72);
-    const size_t o_cnt = take((size_t)cells * 4), o_off = take((size_t)(cells + 1) * 8), o_tsum = take((size_t)(tiles + 1) * 8);
-    if (w) {
-        w->part = (double*)(base + o_part);
-        w->prm = (double*)(base + o_prm);
-        w->flags = (int*)(base + o_flags);
-        w->tri = (double*)(base + o_tri);
-        w->cnt = (unsigned*)(base + o_cnt);
-        w->off = (long long*)(base + o_off);
-        w->tsum = (long long*)(base + o_tsum);
-        w->cells = cells;
-        w->tiles = tiles;
-    }
-    return off;
+// the arrays in the workspace's order; base == nullptr: only the size
+static size_t contains_layout(long nf, int res, ContainsWs& w, char* base) {
+    MeArena a{base};
+    w.cells = (long)res * res;
+    const long tiles = (w.cells + ME_TILE - 1) / ME_TILE;
+    w.part = a.take<double>(ME_BBOX_BLOCKS * 6), w.prm = a.take<double>(8), w.flags = a.take<int>(4);
+    w.tri = a.take<double>(9 * (size_t)nf), w.cnt = a.take<unsigned>(w.cells), w.off = a.take<long long>(w.cells + 1);
+    w.tsum = a.take<long long>(tiles + 1);
+    return a.off;
 }
 
 // scale = (res-1)/(bmax-bmin), translate = 0.5 - scale*bmin (inside_mesh.py:17-18); a flat (or empty) box marks the mesh
 // degenerate: the reference's inf / NaN rescale then fails every point's bbox test (inside_mesh.py:40-41)
 __global__ void me_bbox_final_kernel(const double* __restrict__ part, int nb, double* __restrict__ prm, int res) {
     if (threadIdx.x != 0) return;
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int b = 0; b < nb; ++b)
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fmin(lo[a], part[6 * b + a]);
-            hi[a] = fmax(hi[a], part[6 * b + 3 + a]);
-        }
+    double lo[3], hi[3];
+    me_bbox_fold(part, nb, lo, hi);
     double flat = 0.0;
     for (int a = 0; a < 3; ++a) {
         const double ext = hi[a] - lo[a];
@@ -198,18 +181,19 @@ static int contains_check(long nf, int res, const void* ws, size_t ws_bytes, Con
     S3D_CHECK_ARG(nf >= 0 && nf < (1L << 31), "%s: %ld faces (at most 2^31 - 1)", what, nf);
     S3D_CHECK_ARG(res >= 2 && res <= ME_RES_MAX, "%s: hash_resolution %d outside [2, %d]", what, res, ME_RES_MAX);
     S3D_CHECK_ARG(ws != nullptr, "%s: null workspace", what);
-    const size_t need = contains_layout(nf, res, nullptr, nullptr);
+    const size_t need = contains_layout(nf, res, w, nullptr);
     if (ws_bytes < need) {
         s3d_set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, need);
         return S3D_E_WORKSPACE;
     }
-    contains_layout(nf, res, &w, (char*)ws);
+    contains_layout(nf, res, w, (char*)ws);
     return 0;
 }
 
 extern "C" size_t s3d_mesh_contains_workspace_bytes(long n_faces, int hash_resolution) {
     if (n_faces < 0 || hash_resolution < 2 || hash_resolution > ME_RES_MAX) return 0;
-    return contains_layout(n_faces, hash_resolution, nullptr, nullptr);
+    ContainsWs w;
+    return contains_layout(n_faces, hash_resolution, w, nullptr);
 }
 
 extern "C" int s3d_mesh_contains_build(const double* vertices, long n_vertices, const long long* faces, long n_faces,
@@ -222,39 +206,15 @@ extern "C" int s3d_mesh_contains_build(const double* vertices, long n_vertices, 
     TRY_RET(contains_check(n_faces, hash_resolution, workspace, workspace_bytes, w, "mesh_contains_build"));
     const int res = hash_resolution;
     *n_entries = 0;
-    hipError_t e = hipMemsetAsync(w.flags, 0, 16, st);
-    if (e == hipSuccess) e = hipMemsetAsync(w.cnt, 0, (size_t)w.cells * 4, st);
-    if (e != hipSuccess) {
-        s3d_set_error("mesh_contains_build: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    const int nb = (int)std::min<long>(ME_BBOX_BLOCKS, std::max<long>(1, (3 * n_faces + ME_BLOCK - 1) / ME_BLOCK));
+    S3D_HIP_TRY("mesh_contains_build", hipMemsetAsync(w.flags, 0, 16, st));
+    S3D_HIP_TRY("mesh_contains_build", hipMemsetAsync(w.cnt, 0, (size_t)w.cells * 4, st));
+    const int nb = (int)std::min<long>(ME_BBOX_BLOCKS, me_blocks(3 * n_faces));
     hipLaunchKernelGGL(me_bbox_partial_kernel, dim3(nb), dim3(ME_BLOCK), 0, st, vertices, n_vertices, faces, n_faces,
                        w.part, w.flags);
     hipLaunchKernelGGL(me_bbox_final_kernel, dim3(1), dim3(64), 0, st, w.part, nb, w.prm, res);
     if (n_faces > 0)
-        hipLaunchKernelGGL(me_rescale_count_kernel, dim3((unsigned)((n_faces + ME_BLOCK - 1) / ME_BLOCK)), dim3(ME_BLOCK), 0,
-                           st, vertices, n_vertices, faces, n_faces, w.prm, w.tri, w.cnt, res);
-    me_scan<unsigned, long long, false>(w.cnt, w.off, w.cells, w.tsum, st);
-    S3D_LAUNCH_CHECK();
-    // the scan writes off[0 .. cells); the end of the last cell's list is the grand total
-    e = hipMemcpyAsync(w.off + w.cells, w.tsum + w.tiles, 8, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) {
-        s3d_set_error("mesh_contains_build: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    long long total = 0;
-    int bad = 0;
-    e = hipMemcpyAsync(&total, w.tsum + w.tiles, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, w.flags, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        s3d_set_error("mesh_contains_build: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    S3D_CHECK_ARG(!bad, "mesh_contains_build: a face indexes a vertex outside [0, %ld)", n_vertices);
-    *n_entries = (long)total;
-    return 0;
+        ME_LAUNCH(me_rescale_count_kernel, n_faces, st, vertices, n_vertices, faces, n_faces, w.prm, w.tri, w.cnt, res);
+    return me_lists_finish("mesh_contains_build", w.cnt, w.off, w.cells, w.tsum, w.flags, n_vertices, n_entries, st);
 }
 
 extern "C" int s3d_mesh_contains_fill(long n_faces, int hash_resolution, void* workspace, size_t workspace_bytes,
@@ -264,13 +224,8 @@ extern "C" int s3d_mesh_contains_fill(long n_faces, int hash_resolution, void* w
     S3D_CHECK_ARG(n_entries >= 0 && (n_entries == 0 || entries), "mesh_contains_fill: bad argument");
     TRY_RET(contains_check(n_faces, hash_resolution, workspace, workspace_bytes, w, "mesh_contains_fill"));
     if (n_faces == 0 || n_entries == 0) return 0;
-    hipError_t e = hipMemsetAsync(w.cnt, 0, (size_t)w.cells * 4, st);
-    if (e != hipSuccess) {
-        s3d_set_error("mesh_contains_fill: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    hipLaunchKernelGGL(me_fill_kernel, dim3((unsigned)((n_faces + ME_BLOCK - 1) / ME_BLOCK)), dim3(ME_BLOCK), 0, st, w.tri,
-                       n_faces, w.prm, w.off, w.cnt, entries, (long long)n_entries, hash_resolution);
+    S3D_HIP_TRY("mesh_contains_fill", hipMemsetAsync(w.cnt, 0, (size_t)w.cells * 4, st));
+    ME_LAUNCH(me_fill_kernel, n_faces, st, w.tri, n_faces, w.prm, w.off, w.cnt, entries, (long long)n_entries, hash_resolution);
     S3D_LAUNCH_CHECK();
     return 0;
 }
@@ -284,21 +239,14 @@ extern "C" int s3d_mesh_contains_query(long n_faces, int hash_resolution, const 
     S3D_CHECK_ARG(n_points >= 0 && (n_points == 0 || (points && inside)), "mesh_contains_query: bad argument");
     S3D_CHECK_ARG(n_entries >= 0 && (n_entries == 0 || entries), "mesh_contains_query: bad entries");
     TRY_RET(contains_check(n_faces, hash_resolution, workspace, workspace_bytes, w, "mesh_contains_query"));
-    if (n_disagree) {
-        const hipError_t e = hipMemsetAsync(n_disagree, 0, 8, st);
-        if (e != hipSuccess) {
-            s3d_set_error("mesh_contains_query: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-    }
+    if (n_disagree) S3D_HIP_TRY("mesh_contains_query", hipMemsetAsync(n_disagree, 0, 8, st));
     if (n_points == 0) return 0;
-    const dim3 grid((unsigned)((n_points + ME_BLOCK - 1) / ME_BLOCK));
     if (is_f64)
-        hipLaunchKernelGGL(me_contains_kernel<double>, grid, dim3(ME_BLOCK), 0, st, (const double*)points, n_points, w.prm,
-                           w.tri, w.off, entries, (long long)n_entries, n_faces, hash_resolution, inside, n_disagree);
+        ME_LAUNCH(me_contains_kernel<double>, n_points, st, (const double*)points, n_points, w.prm, w.tri, w.off, entries,
+                  (long long)n_entries, n_faces, hash_resolution, inside, n_disagree);
     else
-        hipLaunchKernelGGL(me_contains_kernel<float>, grid, dim3(ME_BLOCK), 0, st, (const float*)points, n_points, w.prm,
-                           w.tri, w.off, entries, (long long)n_entries, n_faces, hash_resolution, inside, n_disagree);
+        ME_LAUNCH(me_contains_kernel<float>, n_points, st, (const float*)points, n_points, w.prm, w.tri, w.off, entries,
+                  (long long)n_entries, n_faces, hash_resolution, inside, n_disagree);
     S3D_LAUNCH_CHECK();
     return 0;
 }
@@ -388,11 +336,10 @@ extern "C" int s3d_nn_sqdist(const float* a, long na, const float* b, long nb, v
     splits = std::max<long>(1, std::min<long>(splits, 65535));
     const long per_split = ((nb + splits - 1) / splits + NN_TILE - 1) / NN_TILE * NN_TILE;
     splits = (nb + per_split - 1) / per_split;
-    const unsigned g1 = (unsigned)((na + 255) / 256);
-    hipLaunchKernelGGL(nn_init_kernel, dim3(g1), dim3(256), 0, st, best, na);
+    ME_LAUNCH(nn_init_kernel, na, st, best, na);
     hipLaunchKernelGGL(nn_kernel, dim3((unsigned)blocks_a, (unsigned)splits), dim3(ME_BLOCK), 0, st, a, na, b, nb, per_split,
                        best);
-    hipLaunchKernelGGL(nn_unpack_kernel, dim3(g1), dim3(256), 0, st, best, na, d2, idx);
+    ME_LAUNCH(nn_unpack_kernel, na, st, best, na, d2, idx);
     S3D_LAUNCH_CHECK();
     return 0;
 }
@@ -484,13 +431,11 @@ extern "C" int s3d_surface_sample(const double* vertices, long n_vertices, const
     double* area = (double*)workspace;
     double* cdf = (double*)((char*)workspace + me_align((size_t)n_faces * 8));
     double* tsum = (double*)((char*)workspace + 2 * me_align((size_t)n_faces * 8));
-    hipLaunchKernelGGL(me_area_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, st, vertices, n_vertices, faces,
-                       n_faces, area);
+    ME_LAUNCH(me_area_kernel, n_faces, st, vertices, n_vertices, faces, n_faces, area);
     me_scan<double, double, true>(area, cdf, n_faces, tsum, st);
     // the key mixes the seed once, so seeds s and s + 1 do not give streams shifted by one sample
     const unsigned long long key = (seed ^ 0x5851F42D4C957F2Dull) * 0xD1342543DE82EF95ull;
-    hipLaunchKernelGGL(me_sample_kernel, dim3((unsigned)((n_samples + 255) / 256)), dim3(256), 0, st, vertices, faces, n_faces,
-                       area, cdf, n_samples, key, points, face_idx);
+    ME_LAUNCH(me_sample_kernel, n_samples, st, vertices, faces, n_faces, area, cdf, n_samples, key, points, face_idx);
     S3D_LAUNCH_CHECK();
     return 0;
 }

@@ -55,38 +55,20 @@ struct RenderWs {
     unsigned* cnt;         // [tiles] entries per tile, then the fill cursors
     long long* off;        // [tiles + 1]
     long long* tsum;       // [scan tiles + 1]
-    long tiles, scan_tiles;
+    long tiles;
     int tn;                // tiles per image side
 };
-static size_t render_layout(long nv, long nf, int size, int tile, RenderWs* w, char* base) {
-    const int tn = (size + tile - 1) / tile;
-    const long tiles = (long)tn * tn, scan_tiles = (tiles + ME_TILE - 1) / ME_TILE;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += me_align(bytes);
-        return o;
-    };
-    const size_t o_part = take(ME_BBOX_BLOCKS * 6 * 8), o_prm = take(MR_PRM * 8), o_flags = take(16);
-    const size_t o_pv = take((size_t)nv * 24), o_sv = take((size_t)nv * 24), o_tri = take((size_t)nf * 72);
-    const size_t o_rng = take((size_t)nf * 16), o_cnt = take((size_t)tiles * 4), o_off = take((size_t)(tiles + 1) * 8);
-    const size_t o_tsum = take((size_t)(scan_tiles + 1) * 8);
-    if (w) {
-        w->part = (double*)(base + o_part);
-        w->prm = (double*)(base + o_prm);
-        w->flags = (int*)(base + o_flags);
-        w->pv = (double*)(base + o_pv);
-        w->sv = (double*)(base + o_sv);
-        w->tri = (double*)(base + o_tri);
-        w->rng = (int*)(base + o_rng);
-        w->cnt = (unsigned*)(base + o_cnt);
-        w->off = (long long*)(base + o_off);
-        w->tsum = (long long*)(base + o_tsum);
-        w->tiles = tiles;
-        w->scan_tiles = scan_tiles;
-        w->tn = tn;
-    }
-    return off;
+// the arrays in the workspace's order; base == nullptr: only the size
+static size_t render_layout(long nv, long nf, int size, int tile, RenderWs& w, char* base) {
+    MeArena a{base};
+    w.tn = (size + tile - 1) / tile;
+    w.tiles = (long)w.tn * w.tn;
+    const long scan_tiles = (w.tiles + ME_TILE - 1) / ME_TILE;
+    w.part = a.take<double>(ME_BBOX_BLOCKS * 6), w.prm = a.take<double>(MR_PRM), w.flags = a.take<int>(4);
+    w.pv = a.take<double>(3 * (size_t)nv), w.sv = a.take<double>(3 * (size_t)nv), w.tri = a.take<double>(9 * (size_t)nf);
+    w.rng = a.take<int>(4 * (size_t)nf), w.cnt = a.take<unsigned>(w.tiles), w.off = a.take<long long>(w.tiles + 1);
+    w.tsum = a.take<long long>(scan_tiles + 1);
+    return a.off;
 }
 
 // p = (v * scale + t) R + (0, 0, distance); slab coordinates M [c, 1].  Products and sums in index order.
@@ -113,12 +95,8 @@ __global__ __launch_bounds__(ME_BLOCK) void mr_vertex_kernel(const double* __res
 // slab bounds: lo + step * i, step = (hi - lo) / 4; an axis without extent has one slab (bounds +inf)
 __global__ void mr_bounds_kernel(const double* __restrict__ part, int nb, double* __restrict__ prm) {
     if (threadIdx.x != 0) return;
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int b = 0; b < nb; ++b)
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fmin(lo[a], part[6 * b + a]);
-            hi[a] = fmax(hi[a], part[6 * b + 3 + a]);
-        }
+    double lo[3], hi[3];
+    me_bbox_fold(part, nb, lo, hi);
     for (int a = 0; a < 3; ++a) {
         const double step = (hi[a] - lo[a]) / 4.0;
         for (int i = 1; i <= 3; ++i) prm[MR_BND + 3 * a + i - 1] = step == 0.0 ? INFINITY : lo[a] + step * (double)i;
@@ -349,15 +327,6 @@ __global__ __launch_bounds__(ME_BLOCK) void mr_resolve_kernel(const double* __re
     o[3] = (unsigned char)rint(255.0 * (double)count / (double)(S * S));
 }
 
-#define MR_HIP_TRY(what, expr)                                        \
-    do {                                                              \
-        const hipError_t e__ = (expr);                                \
-        if (e__ != hipSuccess) {                                      \
-            s3d_set_error("%s: %s", what, hipGetErrorString(e__));    \
-            return (int)e__;                                          \
-        }                                                             \
-    } while (0)
-
 static bool render_shape_ok(long nv, long nf, int size, int S, int tile) {
     return nv >= 1 && nf >= 1 && nf < (1L << 31) && size >= 1 && size <= MR_SIZE_MAX && (S == 1 || S == 2 || S == 4) &&
            tile >= 1 && (long)tile * S <= 32;
@@ -370,18 +339,19 @@ static int render_check(long nv, long nf, int size, int S, int tile, const void*
     S3D_CHECK_ARG(tile >= 1 && (long)tile * S <= 32, "%s: tile edge %d (1 .. %d pixels at %d samples per pixel edge)", what,
                   tile, 32 / S, S);
     S3D_CHECK_ARG(ws != nullptr, "%s: null workspace", what);
-    const size_t need = render_layout(nv, nf, size, tile, nullptr, nullptr);
+    const size_t need = render_layout(nv, nf, size, tile, w, nullptr);
     if (ws_bytes < need) {
         s3d_set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, need);
         return S3D_E_WORKSPACE;
     }
-    render_layout(nv, nf, size, tile, &w, (char*)ws);
+    render_layout(nv, nf, size, tile, w, (char*)ws);
     return 0;
 }
 
 extern "C" size_t s3d_mesh_render_workspace_bytes(long n_vertices, long n_faces, int size, int samples, int tile) {
     if (!render_shape_ok(n_vertices, n_faces, size, samples, tile)) return 0;
-    return render_layout(n_vertices, n_faces, size, tile, nullptr, nullptr);
+    RenderWs w;
+    return render_layout(n_vertices, n_faces, size, tile, w, nullptr);
 }
 
 extern "C" int s3d_mesh_render_build(const double* vertices, long n_vertices, const long long* faces, long n_faces,
@@ -396,29 +366,16 @@ extern "C" int s3d_mesh_render_build(const double* vertices, long n_vertices, co
     RenderCam cam;
     memcpy(cam.v, camera, sizeof(cam.v));
     for (int k = 0; k < MR_CAM; ++k) S3D_CHECK_ARG(std::isfinite(cam.v[k]), "mesh_render_build: camera value %d is not finite", k);
-    MR_HIP_TRY("mesh_render_build", hipMemsetAsync(w.flags, 0, 16, st));
-    MR_HIP_TRY("mesh_render_build", hipMemsetAsync(w.cnt, 0, (size_t)w.tiles * 4, st));
-    const unsigned vb = (unsigned)((std::max<long>(n_vertices, MR_CAM) + ME_BLOCK - 1) / ME_BLOCK);
-    hipLaunchKernelGGL(mr_vertex_kernel, dim3(vb), dim3(ME_BLOCK), 0, st, vertices, n_vertices, cam, w.prm, w.pv, w.sv);
-    const int nb = (int)std::min<long>(ME_BBOX_BLOCKS, (3 * n_faces + ME_BLOCK - 1) / ME_BLOCK);
+    S3D_HIP_TRY("mesh_render_build", hipMemsetAsync(w.flags, 0, 16, st));
+    S3D_HIP_TRY("mesh_render_build", hipMemsetAsync(w.cnt, 0, (size_t)w.tiles * 4, st));
+    // the first MR_CAM threads also copy the camera into prm
+    ME_LAUNCH(mr_vertex_kernel, std::max<long>(n_vertices, MR_CAM), st, vertices, n_vertices, cam, w.prm, w.pv, w.sv);
+    const int nb = (int)std::min<long>(ME_BBOX_BLOCKS, me_blocks(3 * n_faces));
     hipLaunchKernelGGL(me_bbox_partial_kernel, dim3(nb), dim3(ME_BLOCK), 0, st, w.sv, n_vertices, faces, n_faces, w.part,
                        w.flags);
     hipLaunchKernelGGL(mr_bounds_kernel, dim3(1), dim3(64), 0, st, w.part, nb, w.prm);
-    const unsigned fb = (unsigned)((n_faces + ME_BLOCK - 1) / ME_BLOCK);
-    hipLaunchKernelGGL(mr_face_kernel, dim3(fb), dim3(ME_BLOCK), 0, st, w.pv, n_vertices, faces, n_faces, w.tri, w.rng, w.cnt,
-                       size, tile, w.tn);
-    me_scan<unsigned, long long, false>(w.cnt, w.off, w.tiles, w.tsum, st);
-    S3D_LAUNCH_CHECK();
-    // the scan writes off[0 .. tiles); the end of the last tile's list is the grand total
-    MR_HIP_TRY("mesh_render_build", hipMemcpyAsync(w.off + w.tiles, w.tsum + w.scan_tiles, 8, hipMemcpyDeviceToDevice, st));
-    long long total = 0;
-    int bad = 0;
-    MR_HIP_TRY("mesh_render_build", hipMemcpyAsync(&total, w.tsum + w.scan_tiles, 8, hipMemcpyDeviceToHost, st));
-    MR_HIP_TRY("mesh_render_build", hipMemcpyAsync(&bad, w.flags, 4, hipMemcpyDeviceToHost, st));
-    MR_HIP_TRY("mesh_render_build", hipStreamSynchronize(st));
-    S3D_CHECK_ARG(!bad, "mesh_render_build: a face indexes a vertex outside [0, %ld)", n_vertices);
-    *n_entries = (long)total;
-    return 0;
+    ME_LAUNCH(mr_face_kernel, n_faces, st, w.pv, n_vertices, faces, n_faces, w.tri, w.rng, w.cnt, size, tile, w.tn);
+    return me_lists_finish("mesh_render_build", w.cnt, w.off, w.tiles, w.tsum, w.flags, n_vertices, n_entries, st);
 }
 
 extern "C" int s3d_mesh_render_fill(long n_vertices, long n_faces, int size, int samples, int tile, void* workspace,
@@ -428,9 +385,8 @@ extern "C" int s3d_mesh_render_fill(long n_vertices, long n_faces, int size, int
     S3D_CHECK_ARG(n_entries >= 0 && (n_entries == 0 || entries), "mesh_render_fill: bad argument");
     TRY_RET(render_check(n_vertices, n_faces, size, samples, tile, workspace, workspace_bytes, w, "mesh_render_fill"));
     if (n_entries == 0) return 0;
-    MR_HIP_TRY("mesh_render_fill", hipMemsetAsync(w.cnt, 0, (size_t)w.tiles * 4, st));
-    hipLaunchKernelGGL(mr_fill_kernel, dim3((unsigned)((n_faces + ME_BLOCK - 1) / ME_BLOCK)), dim3(ME_BLOCK), 0, st, w.rng,
-                       n_faces, w.off, w.cnt, entries, (long long)n_entries, w.tn);
+    S3D_HIP_TRY("mesh_render_fill", hipMemsetAsync(w.cnt, 0, (size_t)w.tiles * 4, st));
+    ME_LAUNCH(mr_fill_kernel, n_faces, st, w.rng, n_faces, w.off, w.cnt, entries, (long long)n_entries, w.tn);
     S3D_LAUNCH_CHECK();
     return 0;
 }
@@ -445,14 +401,12 @@ extern "C" int s3d_mesh_render_render(long n_vertices, const long long* faces, l
     S3D_CHECK_ARG(n_entries >= 0 && (n_entries == 0 || entries), "mesh_render_render: bad entries");
     S3D_CHECK_ARG(!vertex_colors || faces, "mesh_render_render: vertex colours need the faces");
     TRY_RET(render_check(n_vertices, n_faces, size, samples, tile, workspace, workspace_bytes, w, "mesh_render_render"));
-    if (n_tests) MR_HIP_TRY("mesh_render_render", hipMemsetAsync(n_tests, 0, 8, st));
+    if (n_tests) S3D_HIP_TRY("mesh_render_render", hipMemsetAsync(n_tests, 0, 8, st));
     const int edge = tile * samples;
     hipLaunchKernelGGL(mr_render_kernel, dim3((unsigned)w.tiles), dim3(edge * edge), 0, st, w.tri, n_faces, w.prm, w.off,
                        entries, (long long)n_entries, size, samples, tile, w.tn, depth, face, n_tests);
     const long px = (long)MR_IMAGES * size * size;
-    if (rgba)
-        hipLaunchKernelGGL(mr_resolve_kernel, dim3((unsigned)((px + ME_BLOCK - 1) / ME_BLOCK)), dim3(ME_BLOCK), 0, st,
-                           w.tri, n_faces, face, faces, vertex_colors, size, samples, rgba);
+    if (rgba) ME_LAUNCH(mr_resolve_kernel, px, st, w.tri, n_faces, face, faces, vertex_colors, size, samples, rgba);
     S3D_LAUNCH_CHECK();
     return 0;
 }

@@ -48,45 +48,25 @@ struct DistWs {
     long long* tsum;       // [tiles + 1]
     unsigned short* skip;  // [cells] Chebyshev distance (in cells) to the nearest occupied cell
     unsigned short* tmp;   // [cells] the transform's second buffer
-    long cells, tiles;
+    long cells;
 };
-static size_t dist_layout(long nf, int res, DistWs* w, char* base) {
-    const long cells = (long)res * res * res, tiles = (cells + ME_TILE - 1) / ME_TILE;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += me_align(bytes);
-        return o;
-    };
-    const size_t o_part = take(ME_BBOX_BLOCKS * 6 * 8), o_prm = take(SD_PRM * 8), o_flags = take(16);
-    const size_t o_tri = take((size_t)nf * 72), o_cnt = take((size_t)cells * 4), o_off = take((size_t)(cells + 1) * 8);
-    const size_t o_tsum = take((size_t)(tiles + 1) * 8), o_skip = take((size_t)cells * 2), o_tmp = take((size_t)cells * 2);
-    if (w) {
-        w->part = (double*)(base + o_part);
-        w->prm = (double*)(base + o_prm);
-        w->flags = (int*)(base + o_flags);
-        w->tri = (double*)(base + o_tri);
-        w->cnt = (unsigned*)(base + o_cnt);
-        w->off = (long long*)(base + o_off);
-        w->tsum = (long long*)(base + o_tsum);
-        w->skip = (unsigned short*)(base + o_skip);
-        w->tmp = (unsigned short*)(base + o_tmp);
-        w->cells = cells;
-        w->tiles = tiles;
-    }
-    return off;
+// the arrays in the workspace's order; base == nullptr: only the size
+static size_t dist_layout(long nf, int res, DistWs& w, char* base) {
+    MeArena a{base};
+    w.cells = (long)res * res * res;
+    const long tiles = (w.cells + ME_TILE - 1) / ME_TILE;
+    w.part = a.take<double>(ME_BBOX_BLOCKS * 6), w.prm = a.take<double>(SD_PRM), w.flags = a.take<int>(4);
+    w.tri = a.take<double>(9 * (size_t)nf), w.cnt = a.take<unsigned>(w.cells), w.off = a.take<long long>(w.cells + 1);
+    w.tsum = a.take<long long>(tiles + 1), w.skip = a.take<unsigned short>(w.cells), w.tmp = a.take<unsigned short>(w.cells);
+    return a.off;
 }
 
 // the grid: res cells per axis over the bounding box; an axis on which the box is flat (or so thin that res / extent
 // overflows) has one cell
 __global__ void sd_grid_kernel(const double* __restrict__ part, int nb, double* __restrict__ prm, int res) {
     if (threadIdx.x != 0) return;
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int b = 0; b < nb; ++b)
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fmin(lo[a], part[6 * b + a]);
-            hi[a] = fmax(hi[a], part[6 * b + 3 + a]);
-        }
+    double lo[3], hi[3];
+    me_bbox_fold(part, nb, lo, hi);
     for (int a = 0; a < 3; ++a) {
         const double ext = hi[a] - lo[a];
         const double ih = (double)res / ext, h = ext / (double)res;
@@ -378,26 +358,19 @@ static int dist_check(long nf, int res, const void* ws, size_t ws_bytes, DistWs&
     S3D_CHECK_ARG(nf >= 1 && nf < (1L << 31), "%s: %ld faces (1 .. 2^31 - 1)", what, nf);
     S3D_CHECK_ARG(res >= 1 && res <= SD_RES_MAX, "%s: resolution %d outside [1, %d]", what, res, SD_RES_MAX);
     S3D_CHECK_ARG(ws != nullptr, "%s: null workspace", what);
-    const size_t need = dist_layout(nf, res, nullptr, nullptr);
+    const size_t need = dist_layout(nf, res, w, nullptr);
     if (ws_bytes < need) {
         s3d_set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, need);
         return S3D_E_WORKSPACE;
     }
-    dist_layout(nf, res, &w, (char*)ws);
+    dist_layout(nf, res, w, (char*)ws);
     return 0;
 }
-#define SD_HIP_TRY(what, expr)                                        \
-    do {                                                              \
-        const hipError_t e__ = (expr);                                \
-        if (e__ != hipSuccess) {                                      \
-            s3d_set_error("%s: %s", what, hipGetErrorString(e__));    \
-            return (int)e__;                                          \
-        }                                                             \
-    } while (0)
 
 extern "C" size_t s3d_mesh_dist_workspace_bytes(long n_faces, int resolution) {
     if (n_faces < 1 || n_faces >= (1L << 31) || resolution < 1 || resolution > SD_RES_MAX) return 0;
-    return dist_layout(n_faces, resolution, nullptr, nullptr);
+    DistWs w;
+    return dist_layout(n_faces, resolution, w, nullptr);
 }
 
 extern "C" int s3d_mesh_dist_build(const double* vertices, long n_vertices, const long long* faces, long n_faces,
@@ -409,31 +382,18 @@ extern "C" int s3d_mesh_dist_build(const double* vertices, long n_vertices, cons
     TRY_RET(dist_check(n_faces, resolution, workspace, workspace_bytes, w, "mesh_dist_build"));
     const int res = resolution;
     *n_entries = 0;
-    SD_HIP_TRY("mesh_dist_build", hipMemsetAsync(w.flags, 0, 16, st));
-    SD_HIP_TRY("mesh_dist_build", hipMemsetAsync(w.cnt, 0, (size_t)w.cells * 4, st));
-    const int nb = (int)std::min<long>(ME_BBOX_BLOCKS, (3 * n_faces + ME_BLOCK - 1) / ME_BLOCK);
+    S3D_HIP_TRY("mesh_dist_build", hipMemsetAsync(w.flags, 0, 16, st));
+    S3D_HIP_TRY("mesh_dist_build", hipMemsetAsync(w.cnt, 0, (size_t)w.cells * 4, st));
+    const int nb = (int)std::min<long>(ME_BBOX_BLOCKS, me_blocks(3 * n_faces));
     hipLaunchKernelGGL(me_bbox_partial_kernel, dim3(nb), dim3(ME_BLOCK), 0, st, vertices, n_vertices, faces, n_faces,
                        w.part, w.flags);
     hipLaunchKernelGGL(sd_grid_kernel, dim3(1), dim3(64), 0, st, w.part, nb, w.prm, res);
-    const unsigned fb = (unsigned)((n_faces + ME_BLOCK - 1) / ME_BLOCK), cb = (unsigned)((w.cells + ME_BLOCK - 1) / ME_BLOCK);
-    hipLaunchKernelGGL(sd_gather_count_kernel, dim3(fb), dim3(ME_BLOCK), 0, st, vertices, n_vertices, faces, n_faces, w.prm,
-                       w.tri, w.cnt, res);
-    me_scan<unsigned, long long, false>(w.cnt, w.off, w.cells, w.tsum, st);
-    // x: counts -> skip, y: skip -> tmp, z: tmp -> skip
-    hipLaunchKernelGGL(sd_skip_pass_kernel, dim3(cb), dim3(ME_BLOCK), 0, st, w.cnt, nullptr, w.skip, w.prm, res, 0);
-    hipLaunchKernelGGL(sd_skip_pass_kernel, dim3(cb), dim3(ME_BLOCK), 0, st, nullptr, w.skip, w.tmp, w.prm, res, 1);
-    hipLaunchKernelGGL(sd_skip_pass_kernel, dim3(cb), dim3(ME_BLOCK), 0, st, nullptr, w.tmp, w.skip, w.prm, res, 2);
-    S3D_LAUNCH_CHECK();
-    // the scan writes off[0 .. cells); the end of the last cell's list is the grand total
-    SD_HIP_TRY("mesh_dist_build", hipMemcpyAsync(w.off + w.cells, w.tsum + w.tiles, 8, hipMemcpyDeviceToDevice, st));
-    long long total = 0;
-    int bad = 0;
-    SD_HIP_TRY("mesh_dist_build", hipMemcpyAsync(&total, w.tsum + w.tiles, 8, hipMemcpyDeviceToHost, st));
-    SD_HIP_TRY("mesh_dist_build", hipMemcpyAsync(&bad, w.flags, 4, hipMemcpyDeviceToHost, st));
-    SD_HIP_TRY("mesh_dist_build", hipStreamSynchronize(st));
-    S3D_CHECK_ARG(!bad, "mesh_dist_build: a face indexes a vertex outside [0, %ld)", n_vertices);
-    *n_entries = (long)total;
-    return 0;
+    ME_LAUNCH(sd_gather_count_kernel, n_faces, st, vertices, n_vertices, faces, n_faces, w.prm, w.tri, w.cnt, res);
+    // x: counts -> skip, y: skip -> tmp, z: tmp -> skip (the passes read the counts, which the scan after them leaves alone)
+    ME_LAUNCH(sd_skip_pass_kernel, w.cells, st, w.cnt, nullptr, w.skip, w.prm, res, 0);
+    ME_LAUNCH(sd_skip_pass_kernel, w.cells, st, nullptr, w.skip, w.tmp, w.prm, res, 1);
+    ME_LAUNCH(sd_skip_pass_kernel, w.cells, st, nullptr, w.tmp, w.skip, w.prm, res, 2);
+    return me_lists_finish("mesh_dist_build", w.cnt, w.off, w.cells, w.tsum, w.flags, n_vertices, n_entries, st);
 }
 
 extern "C" int s3d_mesh_dist_fill(long n_faces, int resolution, void* workspace, size_t workspace_bytes, int* entries,
@@ -443,9 +403,8 @@ extern "C" int s3d_mesh_dist_fill(long n_faces, int resolution, void* workspace,
     S3D_CHECK_ARG(n_entries >= 0 && (n_entries == 0 || entries), "mesh_dist_fill: bad argument");
     TRY_RET(dist_check(n_faces, resolution, workspace, workspace_bytes, w, "mesh_dist_fill"));
     if (n_entries == 0) return 0;
-    SD_HIP_TRY("mesh_dist_fill", hipMemsetAsync(w.cnt, 0, (size_t)w.cells * 4, st));
-    hipLaunchKernelGGL(sd_fill_kernel, dim3((unsigned)((n_faces + ME_BLOCK - 1) / ME_BLOCK)), dim3(ME_BLOCK), 0, st, w.tri,
-                       n_faces, w.prm, w.off, w.cnt, entries, (long long)n_entries, resolution);
+    S3D_HIP_TRY("mesh_dist_fill", hipMemsetAsync(w.cnt, 0, (size_t)w.cells * 4, st));
+    ME_LAUNCH(sd_fill_kernel, n_faces, st, w.tri, n_faces, w.prm, w.off, w.cnt, entries, (long long)n_entries, resolution);
     S3D_LAUNCH_CHECK();
     return 0;
 }
@@ -458,15 +417,14 @@ extern "C" int s3d_mesh_dist_query(long n_faces, int resolution, const void* wor
     S3D_CHECK_ARG(n_points >= 0 && (n_points == 0 || (points && dist)), "mesh_dist_query: bad argument");
     S3D_CHECK_ARG(n_entries >= 0 && (n_entries == 0 || entries), "mesh_dist_query: bad entries");
     TRY_RET(dist_check(n_faces, resolution, workspace, workspace_bytes, w, "mesh_dist_query"));
-    if (n_tests) SD_HIP_TRY("mesh_dist_query", hipMemsetAsync(n_tests, 0, 8, st));
+    if (n_tests) S3D_HIP_TRY("mesh_dist_query", hipMemsetAsync(n_tests, 0, 8, st));
     if (n_points == 0) return 0;
-    const dim3 grid((unsigned)((n_points + ME_BLOCK - 1) / ME_BLOCK));
     if (is_f64)
-        hipLaunchKernelGGL(sd_query_kernel<double>, grid, dim3(ME_BLOCK), 0, st, (const double*)points, n_points, w.prm,
-                           w.tri, w.off, w.skip, entries, (long long)n_entries, n_faces, resolution, dist, face, n_tests);
+        ME_LAUNCH(sd_query_kernel<double>, n_points, st, (const double*)points, n_points, w.prm, w.tri, w.off, w.skip, entries,
+                  (long long)n_entries, n_faces, resolution, dist, face, n_tests);
     else
-        hipLaunchKernelGGL(sd_query_kernel<float>, grid, dim3(ME_BLOCK), 0, st, (const float*)points, n_points, w.prm, w.tri,
-                           w.off, w.skip, entries, (long long)n_entries, n_faces, resolution, dist, face, n_tests);
+        ME_LAUNCH(sd_query_kernel<float>, n_points, st, (const float*)points, n_points, w.prm, w.tri, w.off, w.skip, entries,
+                  (long long)n_entries, n_faces, resolution, dist, face, n_tests);
     S3D_LAUNCH_CHECK();
     return 0;
 }
@@ -567,10 +525,22 @@ __global__ void wn_sum_kernel(const double* __restrict__ part, long n, int n_chu
     w[i] = s / 6.283185307179586;
 }
 
+struct WindingWs {
+    int* flags;            // [0]: a face index outside [0, n_vertices)
+    double* part;          // [n_chunks][points of a pass] chunk sums
+};
+static size_t winding_layout(long nf, long n_points, WindingWs& w, char* base) {
+    MeArena a{base};
+    const long chunk = wn_chunk_faces(nf), n_chunks = (nf + chunk - 1) / chunk;
+    w.flags = a.take<int>(4);
+    w.part = a.take<double>((size_t)n_chunks * (size_t)std::max<long>(1, std::min(n_points, WN_BATCH)));
+    return a.off;
+}
+
 extern "C" size_t s3d_mesh_winding_workspace_bytes(long n_faces, long n_points) {
     if (n_faces < 1 || n_points < 0) return 0;
-    const long chunk = wn_chunk_faces(n_faces), n_chunks = (n_faces + chunk - 1) / chunk;
-    return me_align(16) + me_align((size_t)n_chunks * (size_t)std::max<long>(1, std::min(n_points, WN_BATCH)) * 8);
+    WindingWs w;
+    return winding_layout(n_faces, n_points, w, nullptr);
 }
 
 extern "C" int s3d_mesh_winding(const double* vertices, long n_vertices, const long long* faces, long n_faces,
@@ -582,22 +552,23 @@ extern "C" int s3d_mesh_winding(const double* vertices, long n_vertices, const l
     S3D_CHECK_ARG(n_points >= 0 && n_splits >= 0, "mesh_winding: n_points = %ld, n_splits = %d", n_points, n_splits);
     S3D_CHECK_ARG(vertices && faces && workspace, "mesh_winding: null pointer");
     S3D_CHECK_ARG(n_points == 0 || (points && w), "mesh_winding: null points or output");
-    const size_t need = s3d_mesh_winding_workspace_bytes(n_faces, n_points);
+    WindingWs ws;
+    const size_t need = winding_layout(n_faces, n_points, ws, (char*)workspace);
     if (workspace_bytes < need) {
         s3d_set_error("mesh_winding: workspace %zu < %zu bytes", workspace_bytes, need);
         return S3D_E_WORKSPACE;
     }
     if (n_points == 0) return 0;
-    int* flags = (int*)workspace;
-    double* part = (double*)((char*)workspace + me_align(16));
+    int* const flags = ws.flags;
+    double* const part = ws.part;
     // the faces are validated before any kernel dereferences them (one stream synchronisation)
-    SD_HIP_TRY("mesh_winding", hipMemsetAsync(flags, 0, 16, st));
-    const int cb = (int)std::min<long>(ME_BBOX_BLOCKS, (3 * n_faces + ME_BLOCK - 1) / ME_BLOCK);
+    S3D_HIP_TRY("mesh_winding", hipMemsetAsync(flags, 0, 16, st));
+    const int cb = (int)std::min<long>(ME_BBOX_BLOCKS, me_blocks(3 * n_faces));
     hipLaunchKernelGGL(wn_check_faces_kernel, dim3(cb), dim3(ME_BLOCK), 0, st, faces, n_faces, n_vertices, flags);
     S3D_LAUNCH_CHECK();
     int bad = 0;
-    SD_HIP_TRY("mesh_winding", hipMemcpyAsync(&bad, flags, 4, hipMemcpyDeviceToHost, st));
-    SD_HIP_TRY("mesh_winding", hipStreamSynchronize(st));
+    S3D_HIP_TRY("mesh_winding", hipMemcpyAsync(&bad, flags, 4, hipMemcpyDeviceToHost, st));
+    S3D_HIP_TRY("mesh_winding", hipStreamSynchronize(st));
     S3D_CHECK_ARG(!bad, "mesh_winding: a face indexes a vertex outside [0, %ld)", n_vertices);
 
     const long chunk = wn_chunk_faces(n_faces);
@@ -616,7 +587,7 @@ extern "C" int s3d_mesh_winding(const double* vertices, long n_vertices, const l
         else
             hipLaunchKernelGGL(wn_kernel<float>, grid, dim3(ME_BLOCK), 0, st, (const float*)points + 3 * i0, nb, vertices,
                                faces, n_faces, chunk, n_chunks, cpb, part);
-        hipLaunchKernelGGL(wn_sum_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, part, nb, n_chunks, w + i0);
+        ME_LAUNCH(wn_sum_kernel, nb, st, part, nb, n_chunks, w + i0);
     }
     S3D_LAUNCH_CHECK();
     return 0;

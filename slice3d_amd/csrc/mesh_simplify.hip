@@ -34,33 +34,19 @@ struct SimpWs {
     long nv, nf;
 };
 
-static size_t simp_layout(long nv, long nf, SimpWs* w, char* base) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += me_align(bytes);
-        return at;
-    };
+// the arrays in the workspace's order; base == nullptr: only the size
+static size_t simp_layout(long nv, long nf, SimpWs& w, char* base) {
+    MeArena a{base};
+    const size_t V = (size_t)nv, F = (size_t)nf;
     const long tiles = (std::max(nv + 1, nf) + ME_TILE - 1) / ME_TILE;
-    const size_t flags = take(16 * 4), hdr = take(2 * 8), ksel = take(8);
-    const size_t P = take((size_t)nv * 24), Q = take((size_t)nv * 80), fn = take((size_t)nf * 24), etgt = take((size_t)nf * 72);
-    const size_t border = take((size_t)nv * 4), vcnt = take((size_t)(nv + 1) * 4), voff = take((size_t)(nv + 1) * 4);
-    const size_t vmap = take((size_t)(nv + 1) * 4);
-    const size_t vkey = take((size_t)nv * 8), ekey = take((size_t)nf * 24), wkey = take((size_t)nf * 8);
-    const size_t FA = take((size_t)nf * 12), FB = take((size_t)nf * 12), alive = take((size_t)nf * 4), foff = take((size_t)nf * 4);
-    const size_t adj = take((size_t)nf * 12), erem = take((size_t)nf * 12), wrem = take((size_t)nf * 4);
-    const size_t tsum = take((size_t)(tiles + 1) * 4);
-    if (w) {
-        w->flags = (int*)(base + flags), w->hdr = (long long*)(base + hdr), w->ksel = (ms_u64*)(base + ksel);
-        w->P = (double*)(base + P), w->Q = (double*)(base + Q), w->fn = (double*)(base + fn), w->etgt = (double*)(base + etgt);
-        w->border = (int*)(base + border), w->vcnt = (int*)(base + vcnt), w->voff = (int*)(base + voff);
-        w->vmap = (int*)(base + vmap);
-        w->vkey = (ms_u64*)(base + vkey), w->ekey = (ms_u64*)(base + ekey), w->wkey = (ms_u64*)(base + wkey);
-        w->FA = (int*)(base + FA), w->FB = (int*)(base + FB), w->alive = (int*)(base + alive), w->foff = (int*)(base + foff);
-        w->adj = (int*)(base + adj), w->erem = (int*)(base + erem), w->wrem = (int*)(base + wrem), w->tsum = (int*)(base + tsum);
-        w->nv = nv, w->nf = nf;
-    }
-    return o;
+    w.flags = a.take<int>(16), w.hdr = a.take<long long>(2), w.ksel = a.take<ms_u64>(1);
+    w.P = a.take<double>(3 * V), w.Q = a.take<double>(10 * V), w.fn = a.take<double>(3 * F), w.etgt = a.take<double>(9 * F);
+    w.border = a.take<int>(V), w.vcnt = a.take<int>(V + 1), w.voff = a.take<int>(V + 1), w.vmap = a.take<int>(V + 1);
+    w.vkey = a.take<ms_u64>(V), w.ekey = a.take<ms_u64>(3 * F), w.wkey = a.take<ms_u64>(F);
+    w.FA = a.take<int>(3 * F), w.FB = a.take<int>(3 * F), w.alive = a.take<int>(F), w.foff = a.take<int>(F);
+    w.adj = a.take<int>(3 * F), w.erem = a.take<int>(3 * F), w.wrem = a.take<int>(F), w.tsum = a.take<int>(tiles + 1);
+    w.nv = nv, w.nf = nf;
+    return a.off;
 }
 
 // =============================================================================================
@@ -116,22 +102,11 @@ static __global__ void ms_vsort_kernel(const int* __restrict__ voff, long nv, in
 // =============================================================================================
 // face normals, vertex quadrics, border flags
 // =============================================================================================
-struct ms_v3 {
-    double x, y, z;
-};
-static __device__ __forceinline__ ms_v3 ms_ld(const double* __restrict__ P, int v) {
-    return ms_v3{P[3 * (long)v], P[3 * (long)v + 1], P[3 * (long)v + 2]};
-}
-static __device__ __forceinline__ ms_v3 ms_sub(ms_v3 a, ms_v3 b) { return ms_v3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-static __device__ __forceinline__ double ms_dot(ms_v3 a, ms_v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-static __device__ __forceinline__ ms_v3 ms_cross(ms_v3 a, ms_v3 b) {
-    return ms_v3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
 // unit vector, or 0 with ok = false for a vector without a direction
-static __device__ __forceinline__ ms_v3 ms_unit(ms_v3 a, bool& ok) {
-    const double l = sqrt(ms_dot(a, a));
+static __device__ __forceinline__ me_v3 ms_unit(me_v3 a, bool& ok) {
+    const double l = sqrt(me_dot(a, a));
     ok = l > 0.0 && isfinite(l);
-    return ok ? ms_v3{a.x / l, a.y / l, a.z / l} : ms_v3{0.0, 0.0, 0.0};
+    return ok ? me_v3{a.x / l, a.y / l, a.z / l} : me_v3{0.0, 0.0, 0.0};
 }
 
 // unit normal of every live face (0 for a face without area)
@@ -139,9 +114,9 @@ static __global__ void ms_normals_kernel(const int* __restrict__ F, long nf, con
                                          const int* __restrict__ alive, double* __restrict__ fn) {
     const long f = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nf || !alive[f]) return;
-    const ms_v3 p0 = ms_ld(P, F[3 * f]), p1 = ms_ld(P, F[3 * f + 1]), p2 = ms_ld(P, F[3 * f + 2]);
+    const me_v3 p0 = me_ld(P, F[3 * f]), p1 = me_ld(P, F[3 * f + 1]), p2 = me_ld(P, F[3 * f + 2]);
     bool ok;
-    const ms_v3 n = ms_unit(ms_cross(ms_sub(p1, p0), ms_sub(p2, p0)), ok);
+    const me_v3 n = ms_unit(me_cross(me_sub(p1, p0), me_sub(p2, p0)), ok);
     fn[3 * f] = n.x, fn[3 * f + 1] = n.y, fn[3 * f + 2] = n.z;
 }
 // Simplify.h:637-650: the sum of the plane quadrics of a vertex's faces, in ascending face order
@@ -154,7 +129,7 @@ static __global__ void ms_quadrics_kernel(const int* __restrict__ F, const doubl
     for (int k = voff[v]; k < voff[v + 1]; ++k) {
         const long f = adj[k] >> 2;
         const double a = fn[3 * f], b = fn[3 * f + 1], c = fn[3 * f + 2];
-        const double d = -ms_dot(ms_v3{a, b, c}, ms_ld(P, F[3 * f]));
+        const double d = -me_dot(me_v3{a, b, c}, me_ld(P, F[3 * f]));
         q[0] += a * a, q[1] += a * b, q[2] += a * c, q[3] += a * d;
         q[4] += b * b, q[5] += b * c, q[6] += b * d;
         q[7] += c * c, q[8] += c * d;
@@ -187,13 +162,13 @@ static __device__ __forceinline__ double ms_det3(const double* q, int a11, int a
     return q[a11] * q[a22] * q[a33] + q[a13] * q[a21] * q[a32] + q[a12] * q[a23] * q[a31] - q[a13] * q[a22] * q[a31] -
            q[a11] * q[a23] * q[a32] - q[a12] * q[a21] * q[a33];
 }
-static __device__ __forceinline__ double ms_vertex_error(const double* q, ms_v3 p) {
+static __device__ __forceinline__ double ms_vertex_error(const double* q, me_v3 p) {
     return q[0] * p.x * p.x + 2 * q[1] * p.x * p.y + 2 * q[2] * p.x * p.z + 2 * q[3] * p.x + q[4] * p.y * p.y +
            2 * q[5] * p.y * p.z + 2 * q[6] * p.y + q[7] * p.z * p.z + 2 * q[8] * p.z + q[9];
 }
 // calculate_error (Simplify.h:777-810); a minimiser that is not finite falls through to the three-point choice
 static __device__ double ms_edge_error(const double* __restrict__ Q, const double* __restrict__ P, int a, int b, bool border,
-                                       ms_v3& p) {
+                                       me_v3& p) {
     double q[10];
     for (int i = 0; i < 10; ++i) q[i] = Q[10 * (long)a + i] + Q[10 * (long)b + i];
     const double det = ms_det3(q, 0, 1, 2, 1, 4, 5, 2, 5, 7);
@@ -204,8 +179,8 @@ static __device__ double ms_edge_error(const double* __restrict__ Q, const doubl
         const double err = ms_vertex_error(q, p);
         if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && isfinite(err)) return err;
     }
-    const ms_v3 p1 = ms_ld(P, a), p2 = ms_ld(P, b);
-    const ms_v3 p3 = ms_v3{(p1.x + p2.x) / 2, (p1.y + p2.y) / 2, (p1.z + p2.z) / 2};
+    const me_v3 p1 = me_ld(P, a), p2 = me_ld(P, b);
+    const me_v3 p3 = me_v3{(p1.x + p2.x) / 2, (p1.y + p2.y) / 2, (p1.z + p2.z) / 2};
     const double e1 = ms_vertex_error(q, p1), e2 = ms_vertex_error(q, p2), e3 = ms_vertex_error(q, p3);
     const double err = fmin(e1, fmin(e2, e3));
     p = p1;
@@ -220,7 +195,7 @@ static __device__ double ms_edge_error(const double* __restrict__ Q, const doubl
 //   - the link condition: a vertex next to both endpoints must be the apex of a face on the edge, and no surviving face
 //     around `other` may span the same opposite edge (the collapse would lay two faces on each other).
 static __device__ bool ms_side_legal(const int* __restrict__ F, const double* __restrict__ P, const double* __restrict__ fn,
-                                     const int* __restrict__ voff, const int* __restrict__ adj, int x, int other, ms_v3 p,
+                                     const int* __restrict__ voff, const int* __restrict__ adj, int x, int other, me_v3 p,
                                      int apex0, int apex1, bool link) {
     for (int k = voff[x]; k < voff[x + 1]; ++k) {
         const long g = adj[k] >> 2;
@@ -229,13 +204,13 @@ static __device__ bool ms_side_legal(const int* __restrict__ F, const double* __
         if (id1 == other || id2 == other) continue;
         if (id1 == x || id2 == x) return false;
         bool ok1, ok2, okn;
-        const ms_v3 d1 = ms_unit(ms_sub(ms_ld(P, id1), p), ok1), d2 = ms_unit(ms_sub(ms_ld(P, id2), p), ok2);
+        const me_v3 d1 = ms_unit(me_sub(me_ld(P, id1), p), ok1), d2 = ms_unit(me_sub(me_ld(P, id2), p), ok2);
         if (!ok1 || !ok2) return false;
-        if (fabs(ms_dot(d1, d2)) > 0.999) return false;
-        const ms_v3 n = ms_unit(ms_cross(d1, d2), okn);
+        if (fabs(me_dot(d1, d2)) > 0.999) return false;
+        const me_v3 n = ms_unit(me_cross(d1, d2), okn);
         if (!okn) return false;
-        const ms_v3 old = ms_v3{fn[3 * g], fn[3 * g + 1], fn[3 * g + 2]};
-        if ((old.x != 0 || old.y != 0 || old.z != 0) && !(ms_dot(n, old) >= 0.2)) return false;
+        const me_v3 old = me_v3{fn[3 * g], fn[3 * g + 1], fn[3 * g + 2]};
+        if ((old.x != 0 || old.y != 0 || old.z != 0) && !(me_dot(n, old) >= 0.2)) return false;
         if (!link) continue;
         bool n1 = false, n2 = false;
         for (int m = voff[other]; m < voff[other + 1]; ++m) {
@@ -303,7 +278,7 @@ static __global__ __launch_bounds__(ME_BLOCK) void ms_edges_kernel(
     // interior edges have two faces with two apexes; an edge with one face is a border edge; a chord between two border
     // vertices would pinch the surface
     if (c > 2 || (c == 2 && (apex[0] == apex[1] || border[a]))) return;
-    ms_v3 p;
+    me_v3 p;
     const double cost = ms_edge_error(Q, P, a, b, border[a] != 0, p);
     if (!(cost <= threshold)) return;
     if (!ms_side_legal(F, P, fn, voff, adj, a, b, p, apex[0], apex[1], true)) return;
@@ -425,13 +400,6 @@ static __global__ void ms_header_kernel(long long* __restrict__ hdr, long long n
     hdr[0] = nf_out;
     hdr[1] = vmap[nv];
 }
-static __global__ void ms_emit_vertices_kernel(const double* __restrict__ P, const int* __restrict__ used,
-                                               const int* __restrict__ vmap, long nv, double* __restrict__ out) {
-    const long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= nv || !used[v]) return;
-    const long d = vmap[v];
-    out[3 * d] = P[3 * v], out[3 * d + 1] = P[3 * v + 1], out[3 * d + 2] = P[3 * v + 2];
-}
 static __global__ void ms_emit_faces_kernel(const int* __restrict__ F, const long long* __restrict__ hdr,
                                             const int* __restrict__ vmap, long long* __restrict__ out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -441,42 +409,30 @@ static __global__ void ms_emit_faces_kernel(const int* __restrict__ F, const lon
 // =============================================================================================
 // host
 // =============================================================================================
-#define MS_HIP_TRY(what, expr)                                        \
-    do {                                                              \
-        const hipError_t e__ = (expr);                                \
-        if (e__ != hipSuccess) {                                      \
-            s3d_set_error("%s: %s", what, hipGetErrorString(e__));    \
-            return (int)e__;                                          \
-        }                                                             \
-    } while (0)
-
-static inline unsigned ms_blocks(long n) { return (unsigned)std::max<long>(1, (n + ME_BLOCK - 1) / ME_BLOCK); }
-
 static int simp_check(long nv, long nf, const void* ws, size_t ws_bytes, SimpWs& w, const char* what) {
     S3D_CHECK_ARG(nf >= 1, "%s: the mesh has no face", what);
     S3D_CHECK_ARG(nf < MS_FACES_MAX && nv >= 1 && nv < (1L << 31), "%s: %ld faces, %ld vertices (faces < 2^29, vertices < 2^31)",
                   what, nf, nv);
     S3D_CHECK_ARG(ws != nullptr, "%s: null workspace", what);
-    const size_t need = simp_layout(nv, nf, nullptr, nullptr);
+    const size_t need = simp_layout(nv, nf, w, nullptr);
     S3D_CHECK_ARG(ws_bytes >= need, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
-    simp_layout(nv, nf, &w, (char*)ws);
+    simp_layout(nv, nf, w, (char*)ws);
     return 0;
 }
 
 // alive -> the other face buffer, in order; the live count comes back to the host
 static int ms_compact(SimpWs& w, int*& cur, int*& other, long& live, hipStream_t st) {
     me_scan<int, int, false>(w.alive, w.foff, live, w.tsum, st);
-    hipLaunchKernelGGL(ms_compact_kernel, dim3(ms_blocks(live)), dim3(ME_BLOCK), 0, st, cur, live, w.alive, w.foff, other);
+    ME_LAUNCH(ms_compact_kernel, live, st, cur, live, w.alive, w.foff, other);
     S3D_LAUNCH_CHECK();
-    const long tiles = (live + ME_TILE - 1) / ME_TILE;
     int total = 0;
-    MS_HIP_TRY("mesh_simplify_run", hipMemcpyAsync(&total, w.tsum + tiles, 4, hipMemcpyDeviceToHost, st));
-    MS_HIP_TRY("mesh_simplify_run", hipStreamSynchronize(st));
+    S3D_HIP_TRY("mesh_simplify_run", hipMemcpyAsync(&total, me_scan_total(w.tsum, live), 4, hipMemcpyDeviceToHost, st));
+    S3D_HIP_TRY("mesh_simplify_run", hipStreamSynchronize(st));
     std::swap(cur, other);
     live = total;
     // every listed face is alive again; flags[3] is the count the passes of the next round keep up to date
-    hipLaunchKernelGGL(ms_fill_kernel, dim3(ms_blocks(live)), dim3(ME_BLOCK), 0, st, w.alive, live, 1);
-    hipLaunchKernelGGL(ms_fill_kernel, dim3(1), dim3(ME_BLOCK), 0, st, w.flags + 3, 1L, total);
+    ME_LAUNCH(ms_fill_kernel, live, st, w.alive, live, 1);
+    ME_LAUNCH(ms_fill_kernel, 1L, st, w.flags + 3, 1L, total);
     S3D_LAUNCH_CHECK();
     return 0;
 }
@@ -484,27 +440,24 @@ static int ms_compact(SimpWs& w, int*& cur, int*& other, long& live, hipStream_t
 // One pass over the `listed` faces (the live ones and those that died since the last compaction) at the round's threshold.
 static int ms_pass(SimpWs& w, int* cur, long listed, bool quadrics, long target, double threshold, hipStream_t st) {
     const long nv = w.nv, n3 = 3 * listed;
-    const unsigned eb = ms_blocks(n3), fb = ms_blocks(listed), vb = ms_blocks(nv);
-    MS_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.vcnt, 0, (size_t)(nv + 1) * 4, st));
-    hipLaunchKernelGGL(ms_vcount_kernel, dim3(eb), dim3(ME_BLOCK), 0, st, cur, n3, w.alive, w.vcnt);
+    S3D_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.vcnt, 0, (size_t)(nv + 1) * 4, st));
+    ME_LAUNCH(ms_vcount_kernel, n3, st, cur, n3, w.alive, w.vcnt);
     me_scan<int, int, false>(w.vcnt, w.voff, nv + 1, w.tsum, st);
-    MS_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.vcnt, 0, (size_t)(nv + 1) * 4, st));
-    hipLaunchKernelGGL(ms_vfill_kernel, dim3(eb), dim3(ME_BLOCK), 0, st, cur, n3, w.alive, w.voff, w.vcnt, w.adj);
-    hipLaunchKernelGGL(ms_vsort_kernel, dim3(vb), dim3(ME_BLOCK), 0, st, w.voff, nv, w.adj);
-    hipLaunchKernelGGL(ms_normals_kernel, dim3(fb), dim3(ME_BLOCK), 0, st, cur, listed, w.P, w.alive, w.fn);
+    S3D_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.vcnt, 0, (size_t)(nv + 1) * 4, st));
+    ME_LAUNCH(ms_vfill_kernel, n3, st, cur, n3, w.alive, w.voff, w.vcnt, w.adj);
+    ME_LAUNCH(ms_vsort_kernel, nv, st, w.voff, nv, w.adj);
+    ME_LAUNCH(ms_normals_kernel, listed, st, cur, listed, w.P, w.alive, w.fn);
     if (quadrics)
-        hipLaunchKernelGGL(ms_quadrics_kernel, dim3(vb), dim3(ME_BLOCK), 0, st, cur, w.P, w.fn, w.voff, w.adj, nv, w.Q);
-    MS_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.border, 0, (size_t)nv * 4, st));
-    MS_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.vkey, 0xFF, (size_t)nv * 8, st));
-    MS_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.flags + 1, 0, 8, st));
-    hipLaunchKernelGGL(ms_border_kernel, dim3(eb), dim3(ME_BLOCK), 0, st, cur, n3, w.alive, w.voff, w.adj, w.border);
-    hipLaunchKernelGGL(ms_edges_kernel, dim3(eb), dim3(ME_BLOCK), 0, st, cur, n3, w.P, w.Q, w.fn, w.voff, w.adj, w.border,
-                       w.alive, threshold, w.ekey, w.etgt, w.erem, w.vkey);
-    hipLaunchKernelGGL(ms_winners_kernel, dim3(eb), dim3(ME_BLOCK), 0, st, cur, n3, w.voff, w.adj, w.ekey, w.vkey, w.erem,
-                       w.wkey, w.wrem, w.flags);
+        ME_LAUNCH(ms_quadrics_kernel, nv, st, cur, w.P, w.fn, w.voff, w.adj, nv, w.Q);
+    S3D_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.border, 0, (size_t)nv * 4, st));
+    S3D_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.vkey, 0xFF, (size_t)nv * 8, st));
+    S3D_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.flags + 1, 0, 8, st));
+    ME_LAUNCH(ms_border_kernel, n3, st, cur, n3, w.alive, w.voff, w.adj, w.border);
+    ME_LAUNCH(ms_edges_kernel, n3, st, cur, n3, w.P, w.Q, w.fn, w.voff, w.adj, w.border, w.alive, threshold, w.ekey, w.etgt,
+              w.erem, w.vkey);
+    ME_LAUNCH(ms_winners_kernel, n3, st, cur, n3, w.voff, w.adj, w.ekey, w.vkey, w.erem, w.wkey, w.wrem, w.flags);
     hipLaunchKernelGGL(ms_select_kernel, dim3(1), dim3(ME_BLOCK), 0, st, w.wkey, w.wrem, w.flags, target, w.ksel);
-    hipLaunchKernelGGL(ms_apply_kernel, dim3(eb), dim3(ME_BLOCK), 0, st, cur, n3, w.voff, w.adj, w.ekey, w.erem, w.etgt, w.ksel,
-                       w.P, w.Q, w.alive);
+    ME_LAUNCH(ms_apply_kernel, n3, st, cur, n3, w.voff, w.adj, w.ekey, w.erem, w.etgt, w.ksel, w.P, w.Q, w.alive);
     S3D_LAUNCH_CHECK();
     return 0;
 }
@@ -525,7 +478,8 @@ static int ms_round(SimpWs& w, int* cur, long listed, int k, bool first, long ta
 
 extern "C" size_t s3d_mesh_simplify_workspace_bytes(long n_vertices, long n_faces) {
     if (n_faces < 1 || n_faces >= MS_FACES_MAX || n_vertices < 1 || n_vertices >= (1L << 31)) return 0;
-    return simp_layout(n_vertices, n_faces, nullptr, nullptr);
+    SimpWs w;
+    return simp_layout(n_vertices, n_faces, w, nullptr);
 }
 
 extern "C" int s3d_mesh_simplify_run(const double* vertices, long n_vertices, const long long* faces, long n_faces,
@@ -541,19 +495,19 @@ extern "C" int s3d_mesh_simplify_run(const double* vertices, long n_vertices, co
     *n_rounds = 0;
     const long nv = n_vertices;
     // the indices are checked before anything dereferences them
-    MS_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.flags, 0, 16 * 4, st));
-    hipLaunchKernelGGL(ms_validate_kernel, dim3(ms_blocks(3 * n_faces)), dim3(ME_BLOCK), 0, st, faces, 3 * n_faces, nv, w.flags);
+    S3D_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.flags, 0, 16 * 4, st));
+    ME_LAUNCH(ms_validate_kernel, 3 * n_faces, st, faces, 3 * n_faces, nv, w.flags);
     S3D_LAUNCH_CHECK();
     int bad = 0;
-    MS_HIP_TRY("mesh_simplify_run", hipMemcpyAsync(&bad, w.flags, 4, hipMemcpyDeviceToHost, st));
-    MS_HIP_TRY("mesh_simplify_run", hipStreamSynchronize(st));
+    S3D_HIP_TRY("mesh_simplify_run", hipMemcpyAsync(&bad, w.flags, 4, hipMemcpyDeviceToHost, st));
+    S3D_HIP_TRY("mesh_simplify_run", hipStreamSynchronize(st));
     S3D_CHECK_ARG(!bad, "mesh_simplify_run: a face indexes a vertex outside [0, %ld)", n_vertices);
 
-    MS_HIP_TRY("mesh_simplify_run", hipMemcpyAsync(w.P, vertices, (size_t)nv * 24, hipMemcpyDeviceToDevice, st));
+    S3D_HIP_TRY("mesh_simplify_run", hipMemcpyAsync(w.P, vertices, (size_t)nv * 24, hipMemcpyDeviceToDevice, st));
     int *cur = w.FA, *other = w.FB;
     long live = n_faces;
     const bool work = target_faces < n_faces;
-    hipLaunchKernelGGL(ms_import_kernel, dim3(ms_blocks(live)), dim3(ME_BLOCK), 0, st, faces, live, cur, w.alive, work ? 1 : 0);
+    ME_LAUNCH(ms_import_kernel, live, st, faces, live, cur, w.alive, work ? 1 : 0);
     S3D_LAUNCH_CHECK();
     int rounds = 0;
     if (work) {
@@ -570,16 +524,16 @@ extern "C" int s3d_mesh_simplify_run(const double* vertices, long n_vertices, co
     }
     // s3d_mesh_simplify_emit reads FA
     if (cur != w.FA && live > 0)
-        MS_HIP_TRY("mesh_simplify_run", hipMemcpyAsync(w.FA, cur, (size_t)live * 12, hipMemcpyDeviceToDevice, st));
+        S3D_HIP_TRY("mesh_simplify_run", hipMemcpyAsync(w.FA, cur, (size_t)live * 12, hipMemcpyDeviceToDevice, st));
     // referenced vertices keep their order: used -> vcnt, new index -> vmap
-    MS_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.vcnt, 0, (size_t)(nv + 1) * 4, st));
-    hipLaunchKernelGGL(ms_mark_kernel, dim3(ms_blocks(3 * live)), dim3(ME_BLOCK), 0, st, w.FA, 3 * live, w.vcnt);
+    S3D_HIP_TRY("mesh_simplify_run", hipMemsetAsync(w.vcnt, 0, (size_t)(nv + 1) * 4, st));
+    ME_LAUNCH(ms_mark_kernel, 3 * live, st, w.FA, 3 * live, w.vcnt);
     me_scan<int, int, false>(w.vcnt, w.vmap, nv + 1, w.tsum, st);
     hipLaunchKernelGGL(ms_header_kernel, dim3(1), dim3(1), 0, st, w.hdr, (long long)live, w.vmap, nv);
     S3D_LAUNCH_CHECK();
     int nv_out = 0;
-    MS_HIP_TRY("mesh_simplify_run", hipMemcpyAsync(&nv_out, w.vmap + nv, 4, hipMemcpyDeviceToHost, st));
-    MS_HIP_TRY("mesh_simplify_run", hipStreamSynchronize(st));
+    S3D_HIP_TRY("mesh_simplify_run", hipMemcpyAsync(&nv_out, w.vmap + nv, 4, hipMemcpyDeviceToHost, st));
+    S3D_HIP_TRY("mesh_simplify_run", hipStreamSynchronize(st));
     *n_vertices_out = nv_out;
     *n_faces_out = live;
     *n_rounds = rounds;
@@ -592,9 +546,8 @@ extern "C" int s3d_mesh_simplify_emit(const void* workspace, size_t workspace_by
     SimpWs w;
     TRY_RET(simp_check(n_vertices, n_faces, workspace, workspace_bytes, w, "mesh_simplify_emit"));
     S3D_CHECK_ARG(vertices_out && faces_out, "mesh_simplify_emit: null output");
-    hipLaunchKernelGGL(ms_emit_vertices_kernel, dim3(ms_blocks(n_vertices)), dim3(ME_BLOCK), 0, st, w.P, w.vcnt, w.vmap,
-                       n_vertices, vertices_out);
-    hipLaunchKernelGGL(ms_emit_faces_kernel, dim3(ms_blocks(3 * n_faces)), dim3(ME_BLOCK), 0, st, w.FA, w.hdr, w.vmap, faces_out);
+    ME_LAUNCH(me_emit_vertices_kernel, n_vertices, st, w.P, w.vcnt, w.vmap, n_vertices, vertices_out);
+    ME_LAUNCH(ms_emit_faces_kernel, 3 * n_faces, st, w.FA, w.hdr, w.vmap, faces_out);
     S3D_LAUNCH_CHECK();
     return 0;
 }

@@ -50,40 +50,24 @@ static long tp_hash_size(long nv) {
     return h;
 }
 
-static size_t topo_layout(long nv, long nf, int weld, TopoWs* w, char* base) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += me_align(bytes);
-        return at;
-    };
+// the arrays in the workspace's order; base == nullptr: only the size
+static size_t topo_layout(long nv, long nf, int weld, TopoWs& w, char* base) {
+    MeArena a{base};
+    const size_t V = (size_t)nv, F = (size_t)nf;
     const long tiles = (std::max(nv + 1, nf) + ME_TILE - 1) / ME_TILE;
-    const long chunks = (nf + TP_CHUNK - 1) / TP_CHUNK + 1;
-    const long hsize = weld ? tp_hash_size(nv) : 0;
-    const size_t flags = take(16 * 4), hdr = take(TP_HDR * 8), sumI = take(TP_NI * 8), sumD = take(TP_ND * 8);
-    const size_t tsum = take((size_t)(tiles + 2) * 4);
-    const size_t vmap = take((size_t)nv * 4), W = take((size_t)nf * 12), L = take((size_t)nv * 4), ref = take((size_t)nv * 4);
-    const size_t refw = take((size_t)(nv + 1) * 4), cid = take((size_t)(nv + 1) * 4), vcnt = take((size_t)(nv + 1) * 4);
-    const size_t voff = take((size_t)(nv + 1) * 4), vown = take((size_t)nv * 4), adj = take((size_t)nf * 12);
-    const size_t fcomp = take((size_t)nf * 4), ordA = take((size_t)nf * 4), ordB = take((size_t)nf * 4);
-    const size_t z = take((size_t)nf * 4), zoff = take((size_t)nf * 4), seg = take((size_t)(nf + 1) * 4);
-    const size_t stat = take((size_t)nf * 3);
-    const size_t partI = take((size_t)nf * TP_PI * 4), partD = take((size_t)nf * TP_ND * 8);
-    const size_t spartI = take((size_t)chunks * TP_PI * 4), spartD = take((size_t)chunks * TP_ND * 8);
-    const size_t table = take((size_t)hsize * 4);
-    if (w) {
-        w->flags = (int*)(base + flags), w->hdr = (long long*)(base + hdr);
-        w->sumI = (long long*)(base + sumI), w->sumD = (double*)(base + sumD), w->tsum = (int*)(base + tsum);
-        w->vmap = (int*)(base + vmap), w->W = (int*)(base + W), w->L = (int*)(base + L), w->ref = (int*)(base + ref);
-        w->refw = (int*)(base + refw), w->cid = (int*)(base + cid), w->vcnt = (int*)(base + vcnt), w->voff = (int*)(base + voff);
-        w->vown = (int*)(base + vown), w->adj = (int*)(base + adj), w->fcomp = (int*)(base + fcomp);
-        w->ordA = (int*)(base + ordA), w->ordB = (int*)(base + ordB), w->z = (int*)(base + z), w->zoff = (int*)(base + zoff);
-        w->seg = (int*)(base + seg), w->stat = (unsigned char*)(base + stat);
-        w->partI = (int*)(base + partI), w->partD = (double*)(base + partD);
-        w->spartI = (int*)(base + spartI), w->spartD = (double*)(base + spartD), w->table = (int*)(base + table);
-        w->nv = nv, w->nf = nf, w->hsize = hsize;
-    }
-    return o;
+    const size_t chunks = (size_t)((nf + TP_CHUNK - 1) / TP_CHUNK + 1);
+    w.nv = nv, w.nf = nf, w.hsize = weld ? tp_hash_size(nv) : 0;
+    w.flags = a.take<int>(16), w.hdr = a.take<long long>(TP_HDR), w.sumI = a.take<long long>(TP_NI);
+    w.sumD = a.take<double>(TP_ND), w.tsum = a.take<int>(tiles + 2);
+    w.vmap = a.take<int>(V), w.W = a.take<int>(3 * F), w.L = a.take<int>(V), w.ref = a.take<int>(V);
+    w.refw = a.take<int>(V + 1), w.cid = a.take<int>(V + 1), w.vcnt = a.take<int>(V + 1), w.voff = a.take<int>(V + 1);
+    w.vown = a.take<int>(V), w.adj = a.take<int>(3 * F), w.fcomp = a.take<int>(F), w.ordA = a.take<int>(F);
+    w.ordB = a.take<int>(F), w.z = a.take<int>(F), w.zoff = a.take<int>(F), w.seg = a.take<int>(F + 1);
+    w.stat = a.take<unsigned char>(3 * F);
+    w.partI = a.take<int>(F * TP_PI), w.partD = a.take<double>(F * TP_ND);
+    w.spartI = a.take<int>(chunks * TP_PI), w.spartD = a.take<double>(chunks * TP_ND);
+    w.table = a.take<int>(w.hsize);
+    return a.off;
 }
 
 // =============================================================================================
@@ -279,15 +263,6 @@ static __global__ void tp_split_kernel(const int* __restrict__ order, const int*
 // =============================================================================================
 // table: partial rows over runs of faces, then one row per component
 // =============================================================================================
-struct tp_v3 {
-    double x, y, z;
-};
-static __device__ __forceinline__ tp_v3 tp_ld(const double* __restrict__ P, int v) {
-    return tp_v3{P[3 * (long)v], P[3 * (long)v + 1], P[3 * (long)v + 2]};
-}
-static __device__ __forceinline__ tp_v3 tp_cross(tp_v3 a, tp_v3 b) {
-    return tp_v3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
 // Position p of the ordered face list (order == NULL: the face list itself) heads a run when it starts a chunk of
 // TP_CHUNK positions or a component (fcomp == NULL: one component).  The head's thread walks its run, at most to the
 // chunk's end, and writes the run's sums to row p (by_chunk: row p / TP_CHUNK): integers [vertices, edges, edges with 1,
@@ -322,10 +297,10 @@ static __global__ __launch_bounds__(ME_BLOCK) void tp_partial_kernel(const int* 
         }
         cnt[6] += i0 == i1 || i1 == i2 || i0 == i2;
         cnt[7] += 1;
-        const tp_v3 v0 = tp_ld(P, i0), v1 = tp_ld(P, i1), v2 = tp_ld(P, i2);
-        const tp_v3 n = tp_cross(tp_v3{v1.x - v0.x, v1.y - v0.y, v1.z - v0.z}, tp_v3{v2.x - v0.x, v2.y - v0.y, v2.z - v0.z});
+        const me_v3 v0 = me_ld(P, i0), v1 = me_ld(P, i1), v2 = me_ld(P, i2);
+        const me_v3 n = me_cross(me_v3{v1.x - v0.x, v1.y - v0.y, v1.z - v0.z}, me_v3{v2.x - v0.x, v2.y - v0.y, v2.z - v0.z});
         area += 0.5 * sqrt(n.x * n.x + n.y * n.y + n.z * n.z);
-        const tp_v3 m = tp_cross(v1, v2);
+        const me_v3 m = me_cross(v1, v2);
         det += (v0.x * m.x + v0.y * m.y + v0.z * m.z) / 6.0;   // the volume term det(v0, v1, v2) / 6, then the sum
         lo[0] = fmin(lo[0], fmin(v0.x, fmin(v1.x, v2.x))), hi[0] = fmax(hi[0], fmax(v0.x, fmax(v1.x, v2.x)));
         lo[1] = fmin(lo[1], fmin(v0.y, fmin(v1.y, v2.y))), hi[1] = fmax(hi[1], fmax(v0.y, fmax(v1.y, v2.y)));
@@ -403,13 +378,6 @@ static __global__ void tp_run_header_kernel(long long* __restrict__ hdr, long lo
     hdr[3] = K, hdr[4] = nv, hdr[5] = nf, hdr[6] = weld;
     hdr[2] = TP_MAGIC;
 }
-static __global__ void tp_keep_vertices_kernel(const double* __restrict__ P, const int* __restrict__ used, const int* __restrict__ vnew,
-                                               long nv, double* __restrict__ out) {
-    const long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= nv || !used[v]) return;
-    const long d = vnew[v];
-    out[3 * d] = P[3 * v], out[3 * d + 1] = P[3 * v + 1], out[3 * d + 2] = P[3 * v + 2];
-}
 static __global__ void tp_keep_emit_faces_kernel(const int* __restrict__ W, const int* __restrict__ kept, const int* __restrict__ foff,
                                                  const int* __restrict__ vnew, long nf, long long* __restrict__ out) {
     const long f = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -421,26 +389,14 @@ static __global__ void tp_keep_emit_faces_kernel(const int* __restrict__ W, cons
 // =============================================================================================
 // host
 // =============================================================================================
-#define TP_HIP_TRY(what, expr)                                        \
-    do {                                                              \
-        const hipError_t e__ = (expr);                                \
-        if (e__ != hipSuccess) {                                      \
-            s3d_set_error("%s: %s", what, hipGetErrorString(e__));    \
-            return (int)e__;                                          \
-        }                                                             \
-    } while (0)
-
-static inline unsigned tp_blocks(long n) { return (unsigned)std::max<long>(1, (n + ME_BLOCK - 1) / ME_BLOCK); }
-#define TP_LAUNCH(kernel, n, st, ...) hipLaunchKernelGGL(kernel, dim3(tp_blocks(n)), dim3(ME_BLOCK), 0, st, __VA_ARGS__)
-
 static bool tp_sizes_ok(long nv, long nf) { return nf >= 0 && nf < TP_FACES_MAX && nv >= 0 && nv < (1L << 30); }
 
 static int topo_check(long nv, long nf, int weld, const void* ws, size_t ws_bytes, TopoWs& w, const char* what) {
     S3D_CHECK_ARG(tp_sizes_ok(nv, nf), "%s: %ld faces, %ld vertices (faces < 2^29, vertices < 2^30)", what, nf, nv);
     S3D_CHECK_ARG(ws != nullptr, "%s: null workspace", what);
-    const size_t need = topo_layout(nv, nf, weld, nullptr, nullptr);
+    const size_t need = topo_layout(nv, nf, weld, w, nullptr);
     S3D_CHECK_ARG(ws_bytes >= need, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
-    topo_layout(nv, nf, weld, &w, (char*)ws);
+    topo_layout(nv, nf, weld, w, (char*)ws);
     return 0;
 }
 
@@ -449,8 +405,8 @@ static int topo_check(long nv, long nf, int weld, const void* ws, size_t ws_byte
 // before this has passed.
 static int topo_state(const TopoWs& w, int weld, long n_components, bool kept, const char* what, hipStream_t st) {
     long long h[TP_HDR];
-    TP_HIP_TRY(what, hipMemcpyAsync(h, w.hdr, sizeof h, hipMemcpyDeviceToHost, st));
-    TP_HIP_TRY(what, hipStreamSynchronize(st));
+    S3D_HIP_TRY(what, hipMemcpyAsync(h, w.hdr, sizeof h, hipMemcpyDeviceToHost, st));
+    S3D_HIP_TRY(what, hipStreamSynchronize(st));
     S3D_CHECK_ARG(h[2] == TP_MAGIC, "%s: no completed s3d_mesh_topology_run on this workspace", what);
     S3D_CHECK_ARG(h[4] == w.nv && h[5] == w.nf && h[6] == weld,
                   "%s: %ld vertices, %ld faces, weld %d, but the run on this workspace had %lld, %lld, %lld", what, w.nv, w.nf,
@@ -462,7 +418,8 @@ static int topo_state(const TopoWs& w, int weld, long n_components, bool kept, c
 
 extern "C" size_t s3d_mesh_topology_workspace_bytes(long n_vertices, long n_faces, int weld) {
     if (!tp_sizes_ok(n_vertices, n_faces)) return 0;
-    return topo_layout(n_vertices, n_faces, weld ? 1 : 0, nullptr, nullptr);
+    TopoWs w;
+    return topo_layout(n_vertices, n_faces, weld ? 1 : 0, w, nullptr);
 }
 
 extern "C" int s3d_mesh_topology_run(const double* vertices, long n_vertices, const long long* faces, long n_faces, int weld,
@@ -480,14 +437,14 @@ extern "C" int s3d_mesh_topology_run(const double* vertices, long n_vertices, co
     if (summary_host)
         for (int i = 0; i < TP_NI; ++i) summary_host[i] = 0;
     const long nv = n_vertices, nf = n_faces, n3 = 3 * n_faces;
-    TP_HIP_TRY(what, hipMemsetAsync(w.hdr, 0, TP_HDR * 8, st));   // no completed run until the last launch says so
-    TP_HIP_TRY(what, hipMemsetAsync(w.flags, 0, 16 * 4, st));
-    TP_HIP_TRY(what, hipMemsetAsync(w.sumI, 0, TP_NI * 8, st));
-    TP_HIP_TRY(what, hipMemsetAsync(w.sumD, 0, TP_ND * 8, st));
+    S3D_HIP_TRY(what, hipMemsetAsync(w.hdr, 0, TP_HDR * 8, st));   // no completed run until the last launch says so
+    S3D_HIP_TRY(what, hipMemsetAsync(w.flags, 0, 16 * 4, st));
+    S3D_HIP_TRY(what, hipMemsetAsync(w.sumI, 0, TP_NI * 8, st));
+    S3D_HIP_TRY(what, hipMemsetAsync(w.sumD, 0, TP_ND * 8, st));
     if (nv > 0) {
-        TP_HIP_TRY(what, hipMemsetAsync(w.ref, 0, (size_t)nv * 4, st));
-        TP_LAUNCH(tp_iota_kernel, nv, st, w.vmap, nv);
-        TP_LAUNCH(tp_iota_kernel, nv, st, w.L, nv);
+        S3D_HIP_TRY(what, hipMemsetAsync(w.ref, 0, (size_t)nv * 4, st));
+        ME_LAUNCH(tp_iota_kernel, nv, st, w.vmap, nv);
+        ME_LAUNCH(tp_iota_kernel, nv, st, w.L, nv);
         S3D_LAUNCH_CHECK();
     }
     if (nf == 0) {
@@ -498,22 +455,22 @@ extern "C" int s3d_mesh_topology_run(const double* vertices, long n_vertices, co
     S3D_CHECK_ARG(nv >= 1, "%s: faces without vertices", what);
 
     // the indices are checked before anything dereferences them
-    TP_LAUNCH(tp_validate_kernel, n3, st, faces, n3, nv, w.ref, w.flags);
-    if (weld) TP_LAUNCH(tp_finite_kernel, nv, st, vertices, w.ref, nv, w.flags);
+    ME_LAUNCH(tp_validate_kernel, n3, st, faces, n3, nv, w.ref, w.flags);
+    if (weld) ME_LAUNCH(tp_finite_kernel, nv, st, vertices, w.ref, nv, w.flags);
     S3D_LAUNCH_CHECK();
     int flags[2] = {0, 0};
-    TP_HIP_TRY(what, hipMemcpyAsync(flags, w.flags, 8, hipMemcpyDeviceToHost, st));
-    TP_HIP_TRY(what, hipStreamSynchronize(st));
+    S3D_HIP_TRY(what, hipMemcpyAsync(flags, w.flags, 8, hipMemcpyDeviceToHost, st));
+    S3D_HIP_TRY(what, hipStreamSynchronize(st));
     S3D_CHECK_ARG(!flags[0], "%s: a face indexes a vertex outside [0, %ld)", what, n_vertices);
     S3D_CHECK_ARG(!flags[1], "%s: a vertex that a face references has a coordinate that is not finite (weld)", what);
 
     if (weld) {
-        TP_HIP_TRY(what, hipMemsetAsync(w.table, 0xFF, (size_t)w.hsize * 4, st));
-        TP_LAUNCH(tp_weld_insert_kernel, nv, st, vertices, w.ref, nv, w.table, w.hsize, w.vmap);
-        TP_LAUNCH(tp_weld_read_kernel, nv, st, w.ref, nv, w.table, w.vmap);
+        S3D_HIP_TRY(what, hipMemsetAsync(w.table, 0xFF, (size_t)w.hsize * 4, st));
+        ME_LAUNCH(tp_weld_insert_kernel, nv, st, vertices, w.ref, nv, w.table, w.hsize, w.vmap);
+        ME_LAUNCH(tp_weld_read_kernel, nv, st, w.ref, nv, w.table, w.vmap);
     }
-    TP_HIP_TRY(what, hipMemsetAsync(w.refw, 0, (size_t)(nv + 1) * 4, st));
-    TP_LAUNCH(tp_import_kernel, n3, st, faces, n3, w.vmap, w.W, w.refw);
+    S3D_HIP_TRY(what, hipMemsetAsync(w.refw, 0, (size_t)(nv + 1) * 4, st));
+    ME_LAUNCH(tp_import_kernel, n3, st, faces, n3, w.vmap, w.W, w.refw);
     S3D_LAUNCH_CHECK();
 
     // components: hook, compress, check in launches of their own; the host reads the verdict once per round
@@ -524,55 +481,54 @@ extern "C" int s3d_mesh_topology_run(const double* vertices, long n_vertices, co
             return S3D_E_ROUNDS;
         }
         ++rounds;
-        TP_HIP_TRY(what, hipMemsetAsync(w.flags + 2, 0, 4, st));
-        TP_LAUNCH(tp_hook_kernel, nf, st, w.W, nf, w.L);
-        TP_LAUNCH(tp_compress_kernel, nv, st, w.L, w.refw, nv);
-        TP_LAUNCH(tp_check_kernel, nf, st, w.W, nf, w.L, w.flags);
+        S3D_HIP_TRY(what, hipMemsetAsync(w.flags + 2, 0, 4, st));
+        ME_LAUNCH(tp_hook_kernel, nf, st, w.W, nf, w.L);
+        ME_LAUNCH(tp_compress_kernel, nv, st, w.L, w.refw, nv);
+        ME_LAUNCH(tp_check_kernel, nf, st, w.W, nf, w.L, w.flags);
         S3D_LAUNCH_CHECK();
         int open = 0;
-        TP_HIP_TRY(what, hipMemcpyAsync(&open, w.flags + 2, 4, hipMemcpyDeviceToHost, st));
-        TP_HIP_TRY(what, hipStreamSynchronize(st));
+        S3D_HIP_TRY(what, hipMemcpyAsync(&open, w.flags + 2, 4, hipMemcpyDeviceToHost, st));
+        S3D_HIP_TRY(what, hipStreamSynchronize(st));
         done = !open;
     }
     // ids in ascending order of the roots, which are the components' smallest welded vertices
-    TP_LAUNCH(tp_roots_kernel, nv + 1, st, w.L, w.refw, nv, w.vcnt);
+    ME_LAUNCH(tp_roots_kernel, nv + 1, st, w.L, w.refw, nv, w.vcnt);
     me_scan<int, int, false>(w.vcnt, w.cid, nv + 1, w.tsum, st);
-    TP_LAUNCH(tp_face_component_kernel, nf, st, w.W, nf, w.L, w.cid, w.fcomp);
+    ME_LAUNCH(tp_face_component_kernel, nf, st, w.W, nf, w.L, w.cid, w.fcomp);
     S3D_LAUNCH_CHECK();
     int K = 0;
-    TP_HIP_TRY(what, hipMemcpyAsync(&K, w.cid + nv, 4, hipMemcpyDeviceToHost, st));
-    TP_HIP_TRY(what, hipStreamSynchronize(st));
+    S3D_HIP_TRY(what, hipMemcpyAsync(&K, w.cid + nv, 4, hipMemcpyDeviceToHost, st));
+    S3D_HIP_TRY(what, hipStreamSynchronize(st));
 
     // vertex -> half-edge lists, half-edge status
-    TP_HIP_TRY(what, hipMemsetAsync(w.vcnt, 0, (size_t)(nv + 1) * 4, st));
-    TP_LAUNCH(tp_vcount_kernel, n3, st, w.W, n3, w.vcnt);
+    S3D_HIP_TRY(what, hipMemsetAsync(w.vcnt, 0, (size_t)(nv + 1) * 4, st));
+    ME_LAUNCH(tp_vcount_kernel, n3, st, w.W, n3, w.vcnt);
     me_scan<int, int, false>(w.vcnt, w.voff, nv + 1, w.tsum, st);
-    TP_HIP_TRY(what, hipMemsetAsync(w.vcnt, 0, (size_t)(nv + 1) * 4, st));
-    TP_HIP_TRY(what, hipMemsetAsync(w.vown, 0x7F, (size_t)nv * 4, st));
-    TP_LAUNCH(tp_vfill_kernel, n3, st, w.W, n3, w.voff, w.vcnt, w.adj, w.vown);
-    TP_LAUNCH(tp_edges_kernel, n3, st, w.W, n3, w.voff, w.adj, w.vown, w.stat);
+    S3D_HIP_TRY(what, hipMemsetAsync(w.vcnt, 0, (size_t)(nv + 1) * 4, st));
+    S3D_HIP_TRY(what, hipMemsetAsync(w.vown, 0x7F, (size_t)nv * 4, st));
+    ME_LAUNCH(tp_vfill_kernel, n3, st, w.W, n3, w.voff, w.vcnt, w.adj, w.vown);
+    ME_LAUNCH(tp_edges_kernel, n3, st, w.W, n3, w.voff, w.adj, w.vown, w.stat);
     S3D_LAUNCH_CHECK();
 
     // faces in component order (stable), then the runs' partial rows; the summary's runs are the chunks of the face list
     int *cur = w.ordA, *other = w.ordB;
-    TP_LAUNCH(tp_iota_kernel, nf, st, cur, nf);
-    const long tiles = (nf + ME_TILE - 1) / ME_TILE;
+    ME_LAUNCH(tp_iota_kernel, nf, st, cur, nf);
     for (int bit = 0; bit < 31 && ((long)K - 1) >> bit; ++bit) {
-        TP_LAUNCH(tp_bit_kernel, nf, st, cur, w.fcomp, nf, bit, w.z);
+        ME_LAUNCH(tp_bit_kernel, nf, st, cur, w.fcomp, nf, bit, w.z);
         me_scan<int, int, false>(w.z, w.zoff, nf, w.tsum, st);
-        TP_LAUNCH(tp_split_kernel, nf, st, cur, w.z, w.zoff, w.tsum + tiles, nf, other);
+        ME_LAUNCH(tp_split_kernel, nf, st, cur, w.z, w.zoff, me_scan_total(w.tsum, nf), nf, other);
         std::swap(cur, other);
     }
-    if (cur != w.ordA) TP_HIP_TRY(what, hipMemcpyAsync(w.ordA, cur, (size_t)nf * 4, hipMemcpyDeviceToDevice, st));
-    TP_LAUNCH(tp_partial_kernel, nf, st, w.ordA, w.fcomp, nf, w.W, w.stat, vertices, 0, w.partI, w.partD, w.seg);
-    TP_LAUNCH(tp_partial_kernel, nf, st, (const int*)nullptr, (const int*)nullptr, nf, w.W, w.stat, vertices, 1, w.spartI,
+    if (cur != w.ordA) S3D_HIP_TRY(what, hipMemcpyAsync(w.ordA, cur, (size_t)nf * 4, hipMemcpyDeviceToDevice, st));
+    ME_LAUNCH(tp_partial_kernel, nf, st, w.ordA, w.fcomp, nf, w.W, w.stat, vertices, 0, w.partI, w.partD, w.seg);
+    ME_LAUNCH(tp_partial_kernel, nf, st, (const int*)nullptr, (const int*)nullptr, nf, w.W, w.stat, vertices, 1, w.spartI,
               w.spartD, (int*)nullptr);
-    TP_LAUNCH(tp_rows_kernel, 1, st, (const int*)nullptr, 1L, nf, 1, w.spartI, w.spartD, w.sumI, w.sumD);
+    ME_LAUNCH(tp_rows_kernel, 1, st, (const int*)nullptr, 1L, nf, 1, w.spartI, w.spartD, w.sumI, w.sumD);
     hipLaunchKernelGGL(tp_run_header_kernel, dim3(1), dim3(1), 0, st, w.hdr, (long long)K, (long long)nv, (long long)nf,
                        (long long)weld);
     S3D_LAUNCH_CHECK();
-    if (summary_host) TP_HIP_TRY(what, hipMemcpyAsync(summary_host, w.sumI, TP_NI * 8, hipMemcpyDeviceToHost, st));
-    TP_HIP_TRY(what, hipStreamSynchronize(st));
+    if (summary_host) S3D_HIP_TRY(what, hipMemcpyAsync(summary_host, w.sumI, TP_NI * 8, hipMemcpyDeviceToHost, st));
+    S3D_HIP_TRY(what, hipStreamSynchronize(st));
     *n_components = K;
     *n_rounds = rounds;
     return 0;
@@ -586,9 +542,9 @@ extern "C" int s3d_mesh_topology_emit_labels(const void* workspace, size_t works
     TopoWs w;
     TRY_RET(topo_check(n_vertices, n_faces, weld ? 1 : 0, workspace, workspace_bytes, w, what));
     TRY_RET(topo_state(w, weld ? 1 : 0, -1, false, what, st));
-    if (n_faces > 0 && face_component) TP_LAUNCH(tp_emit_face_labels_kernel, n_faces, st, w.fcomp, n_faces, face_component);
+    if (n_faces > 0 && face_component) ME_LAUNCH(tp_emit_face_labels_kernel, n_faces, st, w.fcomp, n_faces, face_component);
     if (n_vertices > 0 && (vmap || vertex_component))
-        TP_LAUNCH(tp_emit_vertex_labels_kernel, n_vertices, st, w.ref, w.vmap, w.L, w.cid, n_vertices, vmap, vertex_component);
+        ME_LAUNCH(tp_emit_vertex_labels_kernel, n_vertices, st, w.ref, w.vmap, w.L, w.cid, n_vertices, vmap, vertex_component);
     S3D_LAUNCH_CHECK();
     return 0;
 }
@@ -603,10 +559,10 @@ extern "C" int s3d_mesh_topology_emit_table(const void* workspace, size_t worksp
     S3D_CHECK_ARG(n_components >= 0, "%s: %ld components", what, n_components);
     TRY_RET(topo_state(w, weld ? 1 : 0, n_components, false, what, st));
     if (n_components > 0)
-        TP_LAUNCH(tp_rows_kernel, n_components, st, w.seg, n_components, n_faces, 0, w.partI, w.partD, counts, measures);
+        ME_LAUNCH(tp_rows_kernel, n_components, st, w.seg, n_components, n_faces, 0, w.partI, w.partD, counts, measures);
     S3D_LAUNCH_CHECK();
-    TP_HIP_TRY(what, hipMemcpyAsync(counts + TP_NI * n_components, w.sumI, TP_NI * 8, hipMemcpyDeviceToDevice, st));
-    TP_HIP_TRY(what, hipMemcpyAsync(measures + TP_ND * n_components, w.sumD, TP_ND * 8, hipMemcpyDeviceToDevice, st));
+    S3D_HIP_TRY(what, hipMemcpyAsync(counts + TP_NI * n_components, w.sumI, TP_NI * 8, hipMemcpyDeviceToDevice, st));
+    S3D_HIP_TRY(what, hipMemcpyAsync(measures + TP_ND * n_components, w.sumD, TP_ND * 8, hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
@@ -621,24 +577,23 @@ extern "C" int s3d_mesh_topology_keep_run(void* workspace, size_t workspace_byte
     S3D_CHECK_ARG(n_components >= 0, "%s: %ld components", what, n_components);
     *n_vertices_out = *n_faces_out = 0;
     TRY_RET(topo_state(w, weld ? 1 : 0, n_components, false, what, st));
-    TP_HIP_TRY(what, hipMemsetAsync(w.hdr, 0, 16, st));
-    TP_HIP_TRY(what, hipMemsetAsync(w.hdr + 7, 0, 8, st));
+    S3D_HIP_TRY(what, hipMemsetAsync(w.hdr, 0, 16, st));
+    S3D_HIP_TRY(what, hipMemsetAsync(w.hdr + 7, 0, 8, st));
     if (n_faces == 0 || n_components == 0) return 0;
     S3D_CHECK_ARG(keep != nullptr, "%s: null keep flags", what);
     const long nv = n_vertices, nf = n_faces;
     // kept -> z, its scan -> zoff; used -> vcnt, the new indices -> voff
-    TP_HIP_TRY(what, hipMemsetAsync(w.vcnt, 0, (size_t)(nv + 1) * 4, st));
-    TP_LAUNCH(tp_keep_faces_kernel, nf, st, w.W, w.fcomp, nf, keep, drop_degenerate ? 1 : 0, w.z, w.vcnt);
+    S3D_HIP_TRY(what, hipMemsetAsync(w.vcnt, 0, (size_t)(nv + 1) * 4, st));
+    ME_LAUNCH(tp_keep_faces_kernel, nf, st, w.W, w.fcomp, nf, keep, drop_degenerate ? 1 : 0, w.z, w.vcnt);
     me_scan<int, int, false>(w.z, w.zoff, nf, w.tsum, st);
-    const long tiles = (nf + ME_TILE - 1) / ME_TILE;
     // the face total leaves tsum before the vertex scan reuses it
-    TP_HIP_TRY(what, hipMemcpyAsync(w.flags + 4, w.tsum + tiles, 4, hipMemcpyDeviceToDevice, st));
+    S3D_HIP_TRY(what, hipMemcpyAsync(w.flags + 4, me_scan_total(w.tsum, nf), 4, hipMemcpyDeviceToDevice, st));
     me_scan<int, int, false>(w.vcnt, w.voff, nv + 1, w.tsum, st);
     hipLaunchKernelGGL(tp_keep_header_kernel, dim3(1), dim3(1), 0, st, w.hdr, w.flags + 4, w.voff, nv);
     S3D_LAUNCH_CHECK();
     long long hdr[2] = {0, 0};
-    TP_HIP_TRY(what, hipMemcpyAsync(hdr, w.hdr, 16, hipMemcpyDeviceToHost, st));
-    TP_HIP_TRY(what, hipStreamSynchronize(st));
+    S3D_HIP_TRY(what, hipMemcpyAsync(hdr, w.hdr, 16, hipMemcpyDeviceToHost, st));
+    S3D_HIP_TRY(what, hipStreamSynchronize(st));
     *n_faces_out = (long)hdr[0];
     *n_vertices_out = (long)hdr[1];
     return 0;
@@ -654,8 +609,8 @@ extern "C" int s3d_mesh_topology_keep_emit(const void* workspace, size_t workspa
     S3D_CHECK_ARG(vertices && vertices_out && faces_out, "%s: null mesh or output", what);
     if (n_faces == 0 || n_vertices == 0) return 0;
     TRY_RET(topo_state(w, weld ? 1 : 0, -1, true, what, st));
-    TP_LAUNCH(tp_keep_vertices_kernel, n_vertices, st, vertices, w.vcnt, w.voff, n_vertices, vertices_out);
-    TP_LAUNCH(tp_keep_emit_faces_kernel, n_faces, st, w.W, w.z, w.zoff, w.voff, n_faces, faces_out);
+    ME_LAUNCH(me_emit_vertices_kernel, n_vertices, st, vertices, w.vcnt, w.voff, n_vertices, vertices_out);
+    ME_LAUNCH(tp_keep_emit_faces_kernel, n_faces, st, w.W, w.z, w.zoff, w.voff, n_faces, faces_out);
     S3D_LAUNCH_CHECK();
     return 0;
 }
