@@ -570,6 +570,9 @@ int s3d_nhwc_to_nchw(const float* in, float* out, int n, int c, int h, int w, vo
  * The handle is a small host descriptor; s3d_mise_dev_query / _update synchronise the stream once each
  * (round count / error flag).  Host-side twin (bit-exact order): include/slice3d_mesh.h.
  * ------------------------------------------------------------------------------------------- */
+/* 0 for parameters the unit does not serve: resolution0 < 1, depth outside 0..12, or a grid whose (resolution + 1)^3
+ * points do not fit the int indices used throughout (resolution = resolution0 << depth <= 1289; 1290^3 is the largest
+ * cube below 2^31).  s3d_mise_dev_create refuses the same parameters. */
 size_t s3d_mise_dev_workspace_bytes(int resolution0, int depth);
 void* s3d_mise_dev_create(void* workspace, size_t workspace_bytes, int resolution0, int depth,
                           double threshold, void* stream);            /* NULL on error (s3d_last_error) */
@@ -579,7 +582,9 @@ int s3d_mise_dev_resolution(void* handle);                            /* resolut
 int s3d_mise_dev_query(void* handle, int* idx_out, long capacity, long* n_out, void* stream);
 /* their coordinates as reconstruct.py:160-161 forms them in float32: box*(p/resolution - 0.5) -> qry_out (n,3) */
 int s3d_mise_dev_points(void* handle, const int* idx, long n, float box, float* qry_out, void* stream);
-/* mise.update(points, values) + one refinement step; values = the logits of the points (device) */
+/* mise.update(points, values) + one refinement step; values = the logits of the points (device).  Every index is checked
+ * first: one that is negative, >= (resolution + 1)^3 or names a lattice point the octree has not created yet makes the
+ * call return S3D_E_ARG with the octree unchanged (no value stored, no refinement step). */
 int s3d_mise_dev_update(void* handle, const int* idx, const float* values, long n, void* stream);
 int s3d_mise_dev_update_f64(void* handle, const int* idx, const double* values, long n, void* stream);
 /* mise.to_dense(): (r,r,r) float64, unknown entries forward-filled along x, then y, then z */

@@ -9,7 +9,8 @@
 //         vertices of its edges 6, 5, 10 and of the edges whose owner lies outside the grid), per-cell creation order
 //         and interpolation expression, so vertices and faces come out bit-identical and in the same numbering.
 //
-// Equivalence notes (pinned by tests/test_gpu_mesh.py against goldens made with the reference's compiled libraries):
+// Equivalence notes (pinned by tests/test_gpu_mesh.py and tests/test_gpu_mesh_extract.py against goldens made with the
+// reference's compiled libraries):
 //   * which points a round queries does not depend on the ORDER the previous round's points were inserted in; the
 //     device version returns a round's points in ascending grid index instead of the reference's insertion order —
 //     the same SET every round, the same dense grid at the end.
@@ -91,8 +92,12 @@ static size_t mise_layout(int res0, int depth, MiseDev* m, char* base) {
     return off;
 }
 
+// 0 for sizes the unit does not serve.  Point indices are int everywhere (the idx arrays of query / points / update, the
+// emit kernel), so all (res + 1)^3 points must be addressable by one: res <= 1289.
 extern "C" size_t s3d_mise_dev_workspace_bytes(int resolution0, int depth) {
     if (resolution0 < 1 || depth < 0 || depth > 12 || ((long)resolution0 << depth) > 2047) return 0;
+    const long r1 = ((long)resolution0 << depth) + 1;
+    if (r1 * r1 * r1 > 0x7fffffffL) return 0;
     return mise_layout(resolution0, depth, nullptr, nullptr);
 }
 
@@ -240,16 +245,18 @@ extern "C" int s3d_mise_dev_points(void* workspace, const int* idx, long n, floa
     return 0;
 }
 
-// ---- update: scatter the round's values, then one refinement step ----
-template <typename T>
-__global__ void mise_scatter_kernel(MiseDev m, const int* __restrict__ idx, const T* __restrict__ v, long n, int* bad) {
+// ---- update: check the round's points, scatter their values, then one refinement step ----
+__global__ void mise_validate_kernel(MiseDev m, const int* __restrict__ idx, long n, int* bad) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const long li = idx[i];
-    if (li < 0 || li >= m.n_pts || m.pstate[li] == 0) {   // not a grid point of the octree (the reference raises)
-        *bad = 1;
-        return;
-    }
+    if (li < 0 || li >= m.n_pts || m.pstate[li] == 0) *bad = 1;   // not a grid point of the octree (the reference raises)
+}
+template <typename T>
+__global__ void mise_scatter_kernel(MiseDev m, const int* __restrict__ idx, const T* __restrict__ v, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long li = idx[i];
     m.val[li] = (double)v[i];
     m.pstate[li] = 2;
 }
@@ -309,20 +316,12 @@ static int mise_update_impl(void* workspace, const int* idx, const T* values, lo
     const MiseDev m = *mp;
     int* bad = (int*)(m.blk + m.n_tiles);      // the scan's total word doubles as the error flag between queries
     if (n > 0) {
+        // A refused update leaves the octree as it was: every point is checked before the first value is stored and before
+        // the refinement step runs (the reference raises before it subdivides; a step on its own can split a leaf the previous
+        // one created, where a finer neighbour's known points already lie on its faces).
         (void)hipMemsetAsync(bad, 0, 4, st);
-        hipLaunchKernelGGL(mise_scatter_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m, idx, values,
-                           n, bad);
-    }
-    for (int l = 0; l < m.depth; ++l) {
-        const long s = (long)m.res0 << l, nv = s * s * s;
-        hipLaunchKernelGGL(mise_flag_kernel, dim3((unsigned)((nv + 127) / 128)), dim3(128), 0, st, m, l);
-    }
-    for (int l = 0; l < m.depth; ++l) {
-        const long s = (long)m.res0 << l, nv = s * s * s;
-        hipLaunchKernelGGL(mise_split_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, m, l);
-    }
-    S3D_LAUNCH_CHECK();
-    if (n > 0) {
+        hipLaunchKernelGGL(mise_validate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m, idx, n, bad);
+        S3D_LAUNCH_CHECK();
         int h_bad = 0;
         hipError_t e = hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -334,7 +333,17 @@ static int mise_update_impl(void* workspace, const int* idx, const T* values, lo
             s3d_set_error("mise_dev_update: a point is not in the grid");
             return S3D_E_ARG;
         }
+        hipLaunchKernelGGL(mise_scatter_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m, idx, values, n);
     }
+    for (int l = 0; l < m.depth; ++l) {
+        const long s = (long)m.res0 << l, nv = s * s * s;
+        hipLaunchKernelGGL(mise_flag_kernel, dim3((unsigned)((nv + 127) / 128)), dim3(128), 0, st, m, l);
+    }
+    for (int l = 0; l < m.depth; ++l) {
+        const long s = (long)m.res0 << l, nv = s * s * s;
+        hipLaunchKernelGGL(mise_split_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, m, l);
+    }
+    S3D_LAUNCH_CHECK();
     return 0;
 }
 // values: the network's logits at the points of `idx` (float32, as Generator3D.eval_points returns them)
@@ -445,6 +454,16 @@ __device__ __forceinline__ double mc_at(const McDev& d, int x, int y, int z) {
     const long i = ((long)x * d.gy + y) * d.gz + z;
     return d.is_f64 ? ((const double*)d.grid)[i] : (double)((const float*)d.grid)[i];
 }
+// A NaN coordinate (an edge with a NaN end, or inf / inf between an infinite and another value) with the reference's bits.
+// libmcubes runs on x86-64, whose SSE arithmetic hands on a NaN operand as it is (quieted, sign kept) and makes the negative
+// default NaN for inf / inf.  Here `iso - f1` negates f1's NaN, so the expression alone gives such a vertex the other
+// sign.  (A NaN is never <= iso, so an edge that gets a vertex has at most one NaN end.)
+__device__ __forceinline__ double mc_nan_as_reference(double f1, double f2) {
+    const long long quiet = 0x0008000000000000LL;
+    if (f1 != f1) return __longlong_as_double(__double_as_longlong(f1) | quiet);
+    if (f2 != f2) return __longlong_as_double(__double_as_longlong(f2) | quiet);
+    return __longlong_as_double((long long)0xfff8000000000000ULL);
+}
 // vertices the cell creates itself: edges of its case that it owns (6, 5, 10) or whose owner lies outside the grid
 __device__ __forceinline__ unsigned mc_created_mask(unsigned em, int i, int j, int k) {
     unsigned m = 0;
@@ -526,6 +545,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_emit_kernel(McDev d, double* __re
         const double x2 = (axis == 0 ? i : axis == 1 ? j : k) + c_corner[b][axis] + 0.5;
         const double f1 = v[a], f2 = v[b];
         p[axis] = f2 == f1 ? (x2 + x1) / 2 : (x2 - x1) * (d.iso - f1) / (f2 - f1) + x1;
+        if (p[axis] != p[axis]) p[axis] = mc_nan_as_reference(f1, f2);
         double* o = verts + 3 * (v0 + rank);
         o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
         ++rank;

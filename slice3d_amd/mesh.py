@@ -152,6 +152,10 @@ class DeviceMISE:
         return self._torch.stack([i // (r * r), (i // r) % r, i % r], 1)
 
     def update(self, idx, values):
+        if idx.dtype != self._torch.int32 and idx.numel():      # narrowing would wrap a wide index into the grid
+            lo, hi = int(idx.min()), int(idx.max())
+            if lo < 0 or hi >= (self.resolution + 1) ** 3:
+                raise ValueError("Point not in grid! (index %d)" % (lo if lo < 0 else hi))
         idx = idx.to(device=self.device, dtype=self._torch.int32).contiguous()
         values = values.to(self.device).contiguous().reshape(-1)
         assert values.numel() == idx.numel()
