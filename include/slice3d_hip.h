@@ -442,7 +442,7 @@ size_t s3d_train_workspace_bytes(int batch, int size, long n_qry, int n_slices);
  * atomics — the pyramid-sampling backward writes per-tile partial sums into the workspace and adds them in a fixed order
  * (train_sbd.hip) — so the same inputs, seed and weights give bit-identical losses and gradients, call after call.  Smaller query
  * counts / larger images keep the atomic scatter kernels (gradients equal to fp32 summation-order noise).  The workspace holds
- * 98 KB of partial sums per (object, slice, 16 x 16-bin image tile): 1.2 GB at 4 objects x 12 slices.
+ * 29 824 floats (119 KB) of partial sums per (object, slice, 16 x 16-bin image tile) at size 256: 1.47 GB at 4 objects x 12 slices.
  * prec: S3D_PREC_F32 (exact fp32 MFMAs), S3D_PREC_F16X3 (split precision, fp32-class: the mode every parity test and the
  * reported train_samples_per_s use) or — since version 112 — S3D_PREC_F16: a THROUGHPUT mode in which the decoder's GEMM kernels
  * (FFN forward / data pass / both weight-gradient contractions, the fused attention forward and backward, the row-linear layers and

@@ -13,55 +13,13 @@
 // residual input and as the layout of the LayerNorm reductions (4 lanes per row -> 2 shuffles).
 #include "decode.h"
 #include "attn_last.h"
+#include "query_geom.h"
 
 #define LN_EPS 1e-5f
 
 // ---------------------------------------------------------------------------------------------
 // helpers
 // ---------------------------------------------------------------------------------------------
-struct Tap4 {          // bilinear footprint of one query in one level (grid_sample, align_corners=True)
-    int off[4];        // element offset of the tap pixel (before * C), clamped in-bounds
-    float w[4];        // tap weight, 0 for out-of-bounds taps (padding_mode='zeros')
-};
-
-__device__ __forceinline__ Tap4 make_taps(float gx, float gy, int W, int H) {
-#pragma clang fp contract(off)   // the weights must not depend on which products hipcc decides to fuse in a given caller (round 6: two
-                                 // instantiations of the token builder must produce the same bits)
-    // ATen grid_sampler_unnormalize (align_corners): ((coord + 1) / 2) * (size - 1)
-    const float ix = ((gx + 1.f) / 2.f) * (float)(W - 1);
-    const float iy = ((gy + 1.f) / 2.f) * (float)(H - 1);
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
-    const float xe = x0f + 1.f, ye = y0f + 1.f;
-    Tap4 t;
-    const float wnw = (xe - ix) * (ye - iy), wne = (ix - x0f) * (ye - iy);
-    const float wsw = (xe - ix) * (iy - y0f), wse = (ix - x0f) * (iy - y0f);
-    const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W;
-    const bool vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
-    const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x1, 0), W - 1);
-    const int cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y1, 0), H - 1);
-    t.off[0] = cy0 * W + cx0; t.w[0] = (vx0 && vy0) ? wnw : 0.f;
-    t.off[1] = cy0 * W + cx1; t.w[1] = (vx1 && vy0) ? wne : 0.f;
-    t.off[2] = cy1 * W + cx0; t.w[2] = (vx0 && vy1) ? wsw : 0.f;
-    t.off[3] = cy1 * W + cx1; t.w[3] = (vx1 && vy1) ? wse : 0.f;
-    return t;
-}
-
-// project_coord (models.py:28-36): [x y z 1] @ T(4x3); uv = XY / Z; 2(uv - .5); clamp [-1,1]
-__device__ __forceinline__ void project(const float* T, float x, float y, float z, float& gx, float& gy) {
-    const float X = x * T[0] + y * T[3] + z * T[6] + T[9];
-    const float Y = x * T[1] + y * T[4] + z * T[7] + T[10];
-    const float Z = x * T[2] + y * T[5] + z * T[8] + T[11];
-    gx = fminf(fmaxf(2.f * (X / Z - 0.5f), -1.f), 1.f);
-    gy = fminf(fmaxf(2.f * (Y / Z - 0.5f), -1.f), 1.f);
-}
-
-// torch.linspace(start,end,steps)[i] as ATen computes it (symmetric halves)
-__device__ __forceinline__ float linspace_at(float start, float end, int steps, int i) {
-    const float step = (end - start) / (float)(steps - 1);
-    return i < steps / 2 ? start + step * (float)i : end - step * (float)(steps - i - 1);
-}
-
 // LayerNorm over the 128 channels of a row held as y[8] (f32x4) by the 4 lanes sharing l&15
 __device__ __forceinline__ void layer_norm_row(f32x4 (&y)[8], const float* gamma, const float* beta, int g) {
     float s = 0.f;
@@ -111,26 +69,6 @@ __device__ __forceinline__ void layer_norm_row(f32x4 (&y)[8], const float* gamma
 // a jump of the Morton curve) simply takes the per-lane form for that level, and a query's result does not depend on its
 // group mates (tests/test_gpu_parity.py::test_shared_footprint_sampler_is_bit_identical; s3d_decode_set_shared_footprint(0)
 // forces the per-lane form).  With the staging arrays gone the kernel fits 256 registers: two workgroups per CU.
-struct Foot {            // bilinear footprint of one query in one level, factorised (grid_sample, align_corners=True)
-    int x0, y0;          // floor cell; >= 0 because the grid is clamped to [-1, 1]
-    float wx0, wx1, wy0, wy1;  // column / row factors of the tap weights (make_taps: w = wx * wy), 0 for out-of-bounds columns / rows
-                               // (scalars, not arrays: hipcc turns `g == dx ? wx[0] : g == dx + 1 ? wx[1] : 0` into an indexed scratch read)
-};
-__device__ __forceinline__ Foot make_foot(float gx, float gy, int W, int H) {
-#pragma clang fp contract(off)   // (see make_taps)
-    const float ix = ((gx + 1.f) / 2.f) * (float)(W - 1);
-    const float iy = ((gy + 1.f) / 2.f) * (float)(H - 1);
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    Foot f;
-    f.x0 = (int)x0f; f.y0 = (int)y0f;
-    const int x1 = f.x0 + 1, y1 = f.y0 + 1;
-    const float xe = x0f + 1.f, ye = y0f + 1.f;
-    f.wx0 = (f.x0 >= 0 && f.x0 < W) ? xe - ix : 0.f;
-    f.wx1 = (x1 >= 0 && x1 < W) ? ix - x0f : 0.f;
-    f.wy0 = (f.y0 >= 0 && f.y0 < H) ? ye - iy : 0.f;
-    f.wy1 = (y1 >= 0 && y1 < H) ? iy - y0f : 0.f;
-    return f;
-}
 // min / max over the 16 lanes of a DPP row (the 16 queries of the group; every row of the wave holds the same 16)
 #define S3D_ROW16_REDUCE(v, OP)                                                                         \
     v = OP(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false));  /* quad_perm [1,0,3,2] */     \
@@ -363,28 +301,8 @@ __global__ __launch_bounds__(256, 2) void sample_tokens_kernel(const SampleArgs 
             const int b = (int)(grp / a.groups_per_batch);
             long q = (grp % a.groups_per_batch) * S3D_GROUP + (qi & 15);
             if (q >= a.n_qry) q = a.n_qry - 1;  // padded rows recompute the last query; never stored to sdf
-            if (a.perm) q = a.perm[(long)b * a.n_qry + q];
-            float x, y, z;
-            if (a.qry) {
-                const float* p = a.qry + ((long)b * a.n_qry + q) * 3;
-                x = p[0]; y = p[1]; z = p[2];
-            } else {  // dense grid: x slowest, z fastest (common.py:145-164)
-                const long nn = (long)a.nx * a.nx, ql = q + a.q_offset;
-                const int ixg = (int)(ql / nn), iyg = (int)((ql / a.nx) % a.nx), izg = (int)(ql % a.nx);
-                x = a.box * linspace_at(-0.5f, 0.5f, a.nx, ixg);
-                y = a.box * linspace_at(-0.5f, 0.5f, a.nx, iyg);
-                z = a.box * linspace_at(-0.5f, 0.5f, a.nx, izg);
-            }
-            if (a.flip_yz) {  // mode='test' (models.py:53-56)
-                y = -y; z = -z;
-            } else if (a.rot) {  // qry @ obj_rot_mat (models.py:58-60)
-                const float* R = a.rot + b * 9;
-                const float rx = x * R[0] + y * R[3] + z * R[6];
-                const float ry = x * R[1] + y * R[4] + z * R[7];
-                const float rz = x * R[2] + y * R[5] + z * R[8];
-                x = rx; y = ry; z = rz;
-            }
-            float gx, gy;
+            float x, y, z, gx, gy;
+            query_xyz(a.qry, a.rot, a.flip_yz, a.perm, a.nx, a.box, a.q_offset, b, q, a.n_qry, x, y, z);
             project(a.trans + b * 12, x, y, z, gx, gy);
             s_q[0][qi] = x; s_q[1][qi] = y; s_q[2][qi] = z; s_q[3][qi] = gx; s_q[4][qi] = gy;
         }
@@ -907,15 +825,6 @@ int launch_absorb_last(const float* in_w, const float* in_b, const float* out_w,
 // image-space locality sort of the queries (counting sort, 65536 Morton bins of the projected pixel)
 // ---------------------------------------------------------------------------------------------
 #define QS_BINS 65536
-__device__ __forceinline__ unsigned morton8(unsigned x, unsigned y) {
-    auto spread = [](unsigned v) {
-        v = (v | (v << 4)) & 0x0F0Fu;
-        v = (v | (v << 2)) & 0x3333u;
-        v = (v | (v << 1)) & 0x5555u;
-        return v;
-    };
-    return spread(x) | (spread(y) << 1);
-}
 __global__ void qsort_key_kernel(const float* qry, const float* rot, const float* trans, int flip_yz, int batch,
                                  long n_qry, int* keys, int* hist) {
     const long total = (long)batch * n_qry;
@@ -923,28 +832,15 @@ __global__ void qsort_key_kernel(const float* qry, const float* rot, const float
         const int b = (int)(i / n_qry);
         if (!trans) {   // already-projected coordinates: qry = (B, Q, 2) grid in [-1, 1]
             const float gx = qry[i * 2], gy = qry[i * 2 + 1];
-            const unsigned px = (unsigned)fminf(fmaxf((gx + 1.f) * 127.5f, 0.f), 255.f);
-            const unsigned py = (unsigned)fminf(fmaxf((gy + 1.f) * 127.5f, 0.f), 255.f);
-            const int key = (int)morton8(px, py);
+            const int key = (int)morton8(sort_bin(gx), sort_bin(gy));
             keys[i] = key;
             atomicAdd(&hist[(long)b * QS_BINS + key], 1);
             continue;
         }
-        float x = qry[i * 3], y = qry[i * 3 + 1], z = qry[i * 3 + 2];
-        if (flip_yz) {
-            y = -y; z = -z;
-        } else if (rot) {
-            const float* R = rot + b * 9;
-            const float rx = x * R[0] + y * R[3] + z * R[6];
-            const float ry = x * R[1] + y * R[4] + z * R[7];
-            const float rz = x * R[2] + y * R[5] + z * R[8];
-            x = rx; y = ry; z = rz;
-        }
-        float gx, gy;
+        float x = qry[i * 3], y = qry[i * 3 + 1], z = qry[i * 3 + 2], gx, gy;
+        rotate_query(rot, flip_yz, b, x, y, z);
         project(trans + b * 12, x, y, z, gx, gy);
-        const unsigned px = (unsigned)fminf(fmaxf((gx + 1.f) * 127.5f, 0.f), 255.f);
-        const unsigned py = (unsigned)fminf(fmaxf((gy + 1.f) * 127.5f, 0.f), 255.f);
-        const int key = (int)morton8(px, py);
+        const int key = (int)morton8(sort_bin(gx), sort_bin(gy));
         keys[i] = key;
         atomicAdd(&hist[(long)b * QS_BINS + key], 1);
     }
@@ -1240,31 +1136,6 @@ int launch_sample_planes(const float* plane, const float* grid, float* out, int 
 // =============================================================================================
 // Slices3DGTModel front end (model_gt.py:77-96)
 // =============================================================================================
-__device__ __forceinline__ void gt_query_xyz(const float* qry, const float* rot, int flip_yz, const int* perm,
-                                             int nx, float box, int b, long q, long n_qry, float& x, float& y,
-                                             float& z) {
-    if (perm) q = perm[(long)b * n_qry + q];
-    if (qry) {
-        const float* p = qry + ((long)b * n_qry + q) * 3;
-        x = p[0]; y = p[1]; z = p[2];
-    } else {
-        const long nn = (long)nx * nx;
-        const int ixg = (int)(q / nn), iyg = (int)((q / nx) % nx), izg = (int)(q % nx);
-        x = box * linspace_at(-0.5f, 0.5f, nx, ixg);
-        y = box * linspace_at(-0.5f, 0.5f, nx, iyg);
-        z = box * linspace_at(-0.5f, 0.5f, nx, izg);
-    }
-    if (flip_yz) {
-        y = -y; z = -z;
-    } else if (rot) {
-        const float* R = rot + b * 9;
-        const float rx = x * R[0] + y * R[3] + z * R[6];
-        const float ry = x * R[1] + y * R[4] + z * R[7];
-        const float rz = x * R[2] + y * R[5] + z * R[8];
-        x = rx; y = ry; z = rz;
-    }
-}
-
 // F16: the K = 64 product with the raw conv1_2 level on the f16x3 MFMA (see sample_tokens_kernel: the fp32 form is 128 dependent
 // 8-pass MFMAs per task); a lane then owns 8 consecutive channels of each 32-channel block
 template <bool F16>
@@ -1288,7 +1159,7 @@ __global__ __launch_bounds__(256) void sample_tokens_gt_kernel(const SampleGtArg
         long q = (grp % a.groups_per_batch) * S3D_GROUP + m;
         if (q >= a.n_qry) q = a.n_qry - 1;
         float x, y, z, gx, gy;
-        gt_query_xyz(a.qry, a.rot, a.flip_yz, a.perm, a.nx, a.box, b, q, a.n_qry, x, y, z);
+        query_xyz(a.qry, a.rot, a.flip_yz, a.perm, a.nx, a.box, 0, b, q, a.n_qry, x, y, z);
         project(a.trans + b * 12, x, y, z, gx, gy);
         for (int t = wave; t < T; t += 4) {
             f32x4 acc[8];
@@ -1423,7 +1294,7 @@ __global__ __launch_bounds__(256) void gt_point_tokens_kernel(const GtPointArgs 
         long q = (grp % a.groups_per_batch) * S3D_GROUP + m;
         if (q >= a.n_qry) q = a.n_qry - 1;
         float x, y, z;
-        gt_query_xyz(a.qry, a.rot, a.flip_yz, a.perm, a.nx, a.box, b, q, a.n_qry, x, y, z);
+        query_xyz(a.qry, a.rot, a.flip_yz, a.perm, a.nx, a.box, 0, b, q, a.n_qry, x, y, z);
         s_h1[sub][l] = fmaxf(s_w0[l * 3] * x + s_w0[l * 3 + 1] * y + s_w0[l * 3 + 2] * z + s_b0[l], 0.f);
         __syncthreads();
 #pragma unroll

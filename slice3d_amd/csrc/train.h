@@ -169,10 +169,10 @@ struct SampleBwdArgs {
     long n_qry, groups_per_batch, groups;
     const int* perm;         // optional: token rows are in sorted order, perm[b*Q + slot] = query (s3d_query_sort)
     const int* bin_ends;     // with perm: [B][65536] end offset of every Morton bin (launch_query_sort's ws)
-    float* gxy;              // optional scratch, B * n_qry * 2 floats (with perm): the projected image coordinates of every
-                             // SORTED slot, filled by a pre-pass of launch_sample_bwd — the tiled kernel then loads a slot's
-                             // (gx, gy) with one coalesced read instead of walking perm -> qry -> rotate -> project (three
-                             // dependent global loads) 2 x n_slices times per query
+    float* gxy;              // with perm (required then): scratch of B * n_qry * 2 floats, the projected image coordinates of every
+                             // SORTED slot, filled by a pre-pass of launch_sample_bwd — the tiled and the dense kernel load a
+                             // slot's (gx, gy) with one coalesced read instead of walking perm -> qry -> rotate -> project
+                             // (three dependent global loads) 2 x n_slices times per query
     float* partial;          // optional scratch of sample_bwd_partial_floats(size, B, n_slices) floats (with perm, Slices3DRegModel
                              // levels): the atomic-free form (train_sbd.hip) — every tile writes its footprints to its own slot and
                              // a second kernel adds the slots into the maps in a fixed order: bit-reproducible gradients
@@ -180,10 +180,11 @@ struct SampleBwdArgs {
                              // (S/16 ... S/2), dfine[1] the raw 64-ch conv1_2 map, ws34_t the [4][8] image of Wraw^T
 };
 int launch_sample_bwd(const SampleBwdArgs& a, hipStream_t stream);
-// train_sbd.hip: floats of SampleBwdArgs::partial (0: this size runs the atomic kernels); 1 = launched, 0 = not covered, < 0 error
+// train_sbd.hip: floats of SampleBwdArgs::partial (0: this size runs the atomic kernels).  launch_sample_bwd_dense returns an error
+// code like every launcher; *launched = false (and 0) when it does not cover the call, which then takes the atomic kernels.
+// a.gxy has been filled by the caller (launch_sample_bwd's pre-pass)
 size_t sample_bwd_partial_floats(int S, long batch, int n_slices);
-bool sample_bwd_dense_covers(const SampleBwdArgs& a);
-int launch_sample_bwd_dense(const SampleBwdArgs& a, hipStream_t stream);
+int launch_sample_bwd_dense(const SampleBwdArgs& a, hipStream_t stream, bool* launched);
 int launch_tok0_copy(float* full, float* compact, long groups, int T, int dir, int width, hipStream_t stream);
 // perm (optional): row slot -> query index within the batch item (sorted token order)
 int launch_fc_out_fwd(const float* x, const float* w, const float* b, float* sdf, long rows, long gpb, long n_qry,

@@ -1,6 +1,7 @@
 // train2.hip — decoder-specific backward kernels: pyramid-sampling backward (scatter-add), token-0
 // gather/scatter, fc_out, metrics, VGG input-normalisation backward.
 #include "train.h"
+#include "query_geom.h"
 
 // ---- copies between the token tensor [groups][T][16][128] and its compact token-0 rows [groups*16][128]
 __global__ void tok0_copy_kernel(float* __restrict__ full, float* __restrict__ compact, long groups, int T,
@@ -184,17 +185,8 @@ __global__ void qry_rot_rows_kernel(const float* __restrict__ qry, const float* 
         const long grp = row >> 4, b = grp / gpb, q = (grp % gpb) * 16 + (row & 15);
         f32x4 v = zero4();
         if (q < n_qry) {
-            const float* p = qry + (b * n_qry + (perm ? perm[b * n_qry + q] : q)) * 3;
-            float x = p[0], y = p[1], z = p[2];
-            if (flip_yz) {
-                y = -y; z = -z;
-            } else if (rot) {
-                const float* R = rot + b * 9;
-                const float rx = x * R[0] + y * R[3] + z * R[6];
-                const float ry = x * R[1] + y * R[4] + z * R[7];
-                const float rz = x * R[2] + y * R[5] + z * R[8];
-                x = rx; y = ry; z = rz;
-            }
+            float x, y, z;
+            query_xyz(qry, rot, flip_yz, perm, (int)b, q, n_qry, x, y, z);
             v[0] = x; v[1] = y; v[2] = z;
         }
         st4(out + row * 4, v);
@@ -216,28 +208,6 @@ int launch_qry_rot_rows(const float* qry, const float* rot, int flip_yz, long n_
 //   levels 3-4: d raw34 = Ws34^T dtok (MFMA, Ws34^T fragments in LDS) then scatter with the tap weights
 // fp32 hardware atomics (global_atomic_add_f32): summation order is not deterministic.
 // =============================================================================================
-struct Tap4b {
-    int off[4];
-    float w[4];
-};
-__device__ __forceinline__ Tap4b make_taps_b(float gx, float gy, int W, int H) {
-    const float ix = ((gx + 1.f) / 2.f) * (float)(W - 1);
-    const float iy = ((gy + 1.f) / 2.f) * (float)(H - 1);
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
-    const float xe = x0f + 1.f, ye = y0f + 1.f;
-    Tap4b t;
-    const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W;
-    const bool vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
-    const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x1, 0), W - 1);
-    const int cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y1, 0), H - 1);
-    t.off[0] = cy0 * W + cx0; t.w[0] = (vx0 && vy0) ? (xe - ix) * (ye - iy) : 0.f;
-    t.off[1] = cy0 * W + cx1; t.w[1] = (vx1 && vy0) ? (ix - x0f) * (ye - iy) : 0.f;
-    t.off[2] = cy1 * W + cx0; t.w[2] = (vx0 && vy1) ? (xe - ix) * (iy - y0f) : 0.f;
-    t.off[3] = cy1 * W + cx1; t.w[3] = (vx1 && vy1) ? (ix - x0f) * (iy - y0f) : 0.f;
-    return t;
-}
-
 __device__ __forceinline__ void atomic_add4(float* p, const f32x4 v) {
     unsafeAtomicAdd(p + 0, v[0]);
     unsafeAtomicAdd(p + 1, v[1]);
@@ -270,25 +240,9 @@ __global__ __launch_bounds__(256) void sample_bwd_kernel(const SampleBwdArgs a) 
         const int b = (int)(gi / a.groups_per_batch);
         const long q = (gi % a.groups_per_batch) * S3D_GROUP + m;
         const bool qv = q < a.n_qry;
-        long qc = qv ? q : a.n_qry - 1;
-        if (a.perm) qc = a.perm[(long)b * a.n_qry + qc];
-        const float* p = a.qry + ((long)b * a.n_qry + qc) * 3;
-        float x = p[0], y = p[1], z = p[2];
-        if (a.flip_yz) {
-            y = -y; z = -z;
-        } else if (a.rot) {
-            const float* R = a.rot + b * 9;
-            const float rx = x * R[0] + y * R[3] + z * R[6];
-            const float ry = x * R[1] + y * R[4] + z * R[7];
-            const float rz = x * R[2] + y * R[5] + z * R[8];
-            x = rx; y = ry; z = rz;
-        }
-        const float* Tm = a.trans + b * 12;
-        const float X = x * Tm[0] + y * Tm[3] + z * Tm[6] + Tm[9];
-        const float Y = x * Tm[1] + y * Tm[4] + z * Tm[7] + Tm[10];
-        const float Z = x * Tm[2] + y * Tm[5] + z * Tm[8] + Tm[11];
-        const float gx = fminf(fmaxf(2.f * (X / Z - 0.5f), -1.f), 1.f);
-        const float gy = fminf(fmaxf(2.f * (Y / Z - 0.5f), -1.f), 1.f);
+        float x, y, z, gx, gy;
+        query_xyz(a.qry, a.rot, a.flip_yz, a.perm, b, qv ? q : a.n_qry - 1, a.n_qry, x, y, z);
+        project(a.trans + b * 12, x, y, z, gx, gy);
         for (int t = 1 + wave; t < T; t += 4) {
             const long img = (long)b * a.n_slices + (t - 1);
             const float* dp = a.dX + ((gi * T + t) * S3D_GROUP + m) * 128 + 4 * g;
@@ -309,7 +263,7 @@ __global__ __launch_bounds__(256) void sample_bwd_kernel(const SampleBwdArgs a) 
             for (int l = 0; l < 5; ++l) {
                 const int C = LV::C(l), nv = C / 16;
                 const int W = S >> (4 - l);
-                const Tap4b tp = make_taps_b(gx, gy, W, W);
+                const Tap4 tp = make_taps(gx, gy, W, W);
                 float* base = (l < 3 ? a.dproj[l] : a.dfine[l - 3]) + img * (long)W * W * C + 4 * g;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -328,7 +282,7 @@ __global__ __launch_bounds__(256) void sample_bwd_kernel(const SampleBwdArgs a) 
 // Tiled variant for locality-sorted queries (a.perm / a.bin_ends from launch_query_sort).
 // One workgroup per (batch item, slice image, 16x16-bin image tile): the tile's queries are one contiguous
 // range of the sorted order, their bilinear taps fall into a small per-level pixel footprint
-// (ceil(16 (W-1)/255) + 2 squared), which is accumulated with LDS atomics and flushed to the global
+// (tile_footprint squared, query_geom.h), which is accumulated with LDS atomics and flushed to the global
 // gradient maps once — ~40 global atomics per (query, slice) instead of 1920.
 // ---------------------------------------------------------------------------------------------
 struct SbtGeom {
@@ -342,13 +296,6 @@ struct SbtGeom {
 // fragment reads queued behind it (72 MFMAs taking 8-25 k cycles).  A stride of C + 16 floats moves consecutive pixels by 16
 // banks: four neighbouring pixels x four channel quads per instruction are conflict-free.
 #define SBT_PAD 16
-__device__ __forceinline__ unsigned compact8(unsigned v) {   // even bits of a 16-bit Morton code
-    v &= 0x5555u;
-    v = (v | (v >> 1)) & 0x3333u;
-    v = (v | (v >> 2)) & 0x0F0Fu;
-    v = (v | (v >> 4)) & 0x00FFu;
-    return v;
-}
 struct TapL {
     int lofs[4];   // LDS pixel index inside the footprint, or -1 -> use gofs
     int gofs[4];   // global pixel index
@@ -356,16 +303,12 @@ struct TapL {
     bool ok[4];    // tap lies inside the map (an outside tap has weight 0 and is never written)
 };
 __device__ __forceinline__ TapL make_taps_l(float gx, float gy, int W, int ox, int oy, int fw) {
-    const float ix = ((gx + 1.f) / 2.f) * (float)(W - 1);
-    const float iy = ((gy + 1.f) / 2.f) * (float)(W - 1);
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    const int x0 = (int)x0f, y0 = (int)y0f;
-    const float xe = x0f + 1.f, ye = y0f + 1.f;
-    const float wx[2] = {xe - ix, ix - x0f}, wy[2] = {ye - iy, iy - y0f};
+    const Cell c = level_cell(gx, gy, W, W);
+    const float wx[2] = {c.wx0(), c.wx1()}, wy[2] = {c.wy0(), c.wy1()};
     TapL t;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const int x = x0 + (k & 1), y = y0 + (k >> 1);
+        const int x = c.x0 + (k & 1), y = c.y0 + (k >> 1);
         const bool ok = x >= 0 && x < W && y >= 0 && y < W;
         t.ok[k] = ok;
         t.w[k] = ok ? wx[k & 1] * wy[k >> 1] : 0.f;
@@ -399,30 +342,17 @@ struct SbFold {
 // F16 (split-precision training): the product with W_raw^T runs on the f16x3 MFMA (round 4: cycle stamps showed its fp32 form — 192
 // v_mfma_f32_16x16x4_f32 in chains of 32 dependent instructions per 16-query task, shared by the two waves of a SIMD — at 7 000 to
 // 23 000 of a task's ~50 000 cycles); a lane then reads 8 consecutive channels of each 32-channel block of its dX row.
-// pre-pass of the tiled kernel: gxy[b][slot] = projected, clamped image coordinates of the query in sorted slot `slot`
-// (models.py:28-36 after the rotation of :58-60) — the same expressions, in the same order, as the tiled kernel used in place
+// pre-pass of the tiled and the dense kernel: gxy[b][slot] = projected, clamped image coordinates of the query in sorted slot
+// `slot` (query_xyz and project of query_geom.h: the functions the forward and the sort call)
 __global__ void sbt_project_kernel(const SampleBwdArgs a, int batch) {
     const long total = (long)batch * a.n_qry;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int b = (int)(i / a.n_qry);
-        const long q = a.perm[i];
-        const float* p = a.qry + ((long)b * a.n_qry + q) * 3;
-        const float* Tm = a.trans + b * 12;
-        float x = p[0], y = p[1], z = p[2];
-        if (a.flip_yz) {
-            y = -y; z = -z;
-        } else if (a.rot) {
-            const float* R = a.rot + b * 9;
-            const float rx = x * R[0] + y * R[3] + z * R[6];
-            const float ry = x * R[1] + y * R[4] + z * R[7];
-            const float rz = x * R[2] + y * R[5] + z * R[8];
-            x = rx; y = ry; z = rz;
-        }
-        const float X = x * Tm[0] + y * Tm[3] + z * Tm[6] + Tm[9];
-        const float Y = x * Tm[1] + y * Tm[4] + z * Tm[7] + Tm[10];
-        const float Z = x * Tm[2] + y * Tm[5] + z * Tm[8] + Tm[11];
-        a.gxy[2 * i] = fminf(fmaxf(2.f * (X / Z - 0.5f), -1.f), 1.f);
-        a.gxy[2 * i + 1] = fminf(fmaxf(2.f * (Y / Z - 0.5f), -1.f), 1.f);
+        float x, y, z, gx, gy;
+        query_xyz(a.qry, a.rot, a.flip_yz, a.perm, b, i - (long)b * a.n_qry, a.n_qry, x, y, z);
+        project(a.trans + b * 12, x, y, z, gx, gy);
+        a.gxy[2 * i] = gx;
+        a.gxy[2 * i + 1] = gy;
     }
 }
 
@@ -455,35 +385,15 @@ __global__ __launch_bounds__(SBT_THREADS) void sample_bwd_tiled_kernel(const Sam
     int ox[5], oy[5];
 #pragma unroll
     for (int l = 0; l < 5; ++l) {
-        ox[l] = 16 * tx * (G.W[l] - 1) / 255;
-        oy[l] = 16 * ty * (G.W[l] - 1) / 255;
+        ox[l] = tile_origin(tx, G.W[l]);
+        oy[l] = tile_origin(ty, G.W[l]);
     }
     const long img = (long)b * a.n_slices + ts;
-    const float* Tm = a.trans + b * 12;
-    // image coordinates of sorted slot qs of this object (clamped into the tile's range by the caller)
+    // image coordinates of sorted slot qs of this object (clamped into the tile's range by the caller): the pre-pass's
+    // (sbt_project_kernel), one coalesced 8-byte load
     auto project_slot = [&](long qs, float& gx, float& gy) {
-        if (a.gxy) {   // pre-pass (sbt_project_kernel): one coalesced 8-byte load
-            const s3d_float2 g2 = *reinterpret_cast<const s3d_float2*>(a.gxy + 2 * ((long)b * a.n_qry + qs));
-            gx = g2[0]; gy = g2[1];
-            return;
-        }
-        const long q = a.perm[(long)b * a.n_qry + qs];
-        const float* p = a.qry + ((long)b * a.n_qry + q) * 3;
-        float x = p[0], y = p[1], z = p[2];
-        if (a.flip_yz) {
-            y = -y; z = -z;
-        } else if (a.rot) {
-            const float* R = a.rot + b * 9;
-            const float rx = x * R[0] + y * R[3] + z * R[6];
-            const float ry = x * R[1] + y * R[4] + z * R[7];
-            const float rz = x * R[2] + y * R[5] + z * R[8];
-            x = rx; y = ry; z = rz;
-        }
-        const float X = x * Tm[0] + y * Tm[3] + z * Tm[6] + Tm[9];
-        const float Y = x * Tm[1] + y * Tm[4] + z * Tm[7] + Tm[10];
-        const float Z = x * Tm[2] + y * Tm[5] + z * Tm[8] + Tm[11];
-        gx = fminf(fmaxf(2.f * (X / Z - 0.5f), -1.f), 1.f);
-        gy = fminf(fmaxf(2.f * (Y / Z - 0.5f), -1.f), 1.f);
+        const s3d_float2 g2 = *reinterpret_cast<const s3d_float2*>(a.gxy + 2 * ((long)b * a.n_qry + qs));
+        gx = g2[0]; gy = g2[1];
     };
     auto row_of = [&](long qs) { return ((((long)b * a.groups_per_batch + (qs >> 4)) * T + t) * S3D_GROUP + (qs & 15)) * 128; };
 
@@ -683,18 +593,19 @@ __global__ __launch_bounds__(SBT_THREADS) void sample_bwd_tiled_kernel(const Sam
     }
 }
 
+// the atomic kernels: the tiled one for sorted slots whose footprints fit its registers and LDS, else one group per workgroup
 template <int GT>
 static int launch_sample_bwd_t(const SampleBwdArgs& a, hipStream_t stream) {
     using LV = SbLevels<GT>;
     using FD = SbFold<GT>;
-    if (a.perm && a.bin_ends) {
+    if (a.perm) {
         SbtGeom G;
         int off = 0;
         bool fits = true;
         for (int l = 0; l < 5; ++l) {
             G.W[l] = a.size >> (4 - l);
             G.C[l] = LV::C(l);
-            G.fw[l] = (16 * (G.W[l] - 1) + 254) / 255 + 2;
+            G.fw[l] = tile_footprint(G.W[l]);
             G.off[l] = off;
             if (l >= FD::NF) off += G.fw[l] * G.fw[l] * (G.C[l] + SBT_PAD);       // raw levels: LDS accumulators (padded pixel stride)
             else fits = fits && G.fw[l] * G.fw[l] <= 16 * FD::nmt(l);             // folded levels: register tiles
@@ -706,12 +617,6 @@ static int launch_sample_bwd_t(const SampleBwdArgs& a, hipStream_t stream) {
             TRY_RET(s3d_set_max_lds(attr_done, {(const void*)sample_bwd_tiled_kernel<GT, false>,
                                                 (const void*)sample_bwd_tiled_kernel<GT, true>}, 160 * 1024));
             const long batch = a.groups / a.groups_per_batch;
-            if (a.gxy) {
-                const long total = batch * a.n_qry;
-                hipLaunchKernelGGL(sbt_project_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256),
-                                   0, stream, a, (int)batch);
-                S3D_LAUNCH_CHECK();
-            }
             if (a.ws34_t16)
                 hipLaunchKernelGGL((sample_bwd_tiled_kernel<GT, true>), dim3((unsigned)(batch * a.n_slices * 256)), dim3(SBT_THREADS),
                                    lds, stream, a, G);
@@ -730,20 +635,16 @@ static int launch_sample_bwd_t(const SampleBwdArgs& a, hipStream_t stream) {
 
 int launch_sample_bwd(const SampleBwdArgs& a, hipStream_t stream) {
     if (a.groups <= 0) return 0;
-    if (sample_bwd_dense_covers(a)) {
-        if (a.gxy) {
-            const long batch = a.groups / a.groups_per_batch, total = batch * a.n_qry;
-            hipLaunchKernelGGL(sbt_project_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0,
-                               stream, a, (int)batch);
-            S3D_LAUNCH_CHECK();
-        }
-        const int r = launch_sample_bwd_dense(a, stream);
-        if (r < 0) {
-            s3d_set_error("sample_bwd_dense launch failed: %s", hipGetErrorString(hipGetLastError()));
-            return 1;
-        }
-        if (r > 0) return 0;
+    S3D_CHECK_ARG(!a.perm || (a.gxy && a.bin_ends), "sample_bwd: perm needs gxy and bin_ends");
+    if (a.perm) {   // the sorted slots' image coordinates, for whichever of the dense and the tiled kernel runs
+        const long batch = a.groups / a.groups_per_batch, total = batch * a.n_qry;
+        hipLaunchKernelGGL(sbt_project_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0,
+                           stream, a, (int)batch);
+        S3D_LAUNCH_CHECK();
     }
+    bool done = false;
+    TRY_RET(launch_sample_bwd_dense(a, stream, &done));
+    if (done) return 0;
     return a.gt ? launch_sample_bwd_t<1>(a, stream) : launch_sample_bwd_t<0>(a, stream);
 }
 

@@ -28,6 +28,7 @@
 // (-DSBD_STAMPS, tools/r06_sbd_stamps.sh): 71 % of a workgroup's time in the k-steps, whose raw-level part is bound by its scalar
 // bit tests and taken branches (39 conditional MFMA sites), not by the matrix pipe (29 % busy) or LDS.
 #include "train.h"
+#include "query_geom.h"
 
 #define SBD_THREADS 512
 #define SBD_CHUNK 64          // queries per staged chunk = 16 k-steps
@@ -50,19 +51,6 @@ __host__ __device__ static constexpr int sbd_mt0(int l) { return l == 0 ? 0 : l 
 __host__ __device__ static constexpr int sbd_nmt(int l) { return l < 2 ? 1 : 3; }
 __host__ __device__ static constexpr int sbd_C(int l) { return l < 3 ? 128 : (l == 3 ? 64 : 32); }
 
-__device__ __forceinline__ unsigned sbd_compact8(unsigned v) {
-    v &= 0x5555u;
-    v = (v | (v >> 1)) & 0x3333u;
-    v = (v | (v >> 2)) & 0x0F0Fu;
-    v = (v | (v >> 4)) & 0x00FFu;
-    return v;
-}
-__device__ __forceinline__ unsigned sbd_spread8(unsigned v) {
-    v = (v | (v << 4)) & 0x0F0Fu;
-    v = (v | (v << 2)) & 0x3333u;
-    v = (v | (v << 1)) & 0x5555u;
-    return v;
-}
 // element (k, c') of W_raw^T in the fp32 fragment image (tile u = c' / 16 of the level's first tile u0; common.h's swapped form)
 __device__ __forceinline__ float sbd_wraw(const float* img, int u0, int k, int c) {
     const int u = u0 + (c >> 4), mm = c & 15;
@@ -191,32 +179,12 @@ __global__ __launch_bounds__(SBD_THREADS) void sample_bwd_dense_kernel(const Sam
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = lane & 15, g = lane >> 4;
     const int T = a.n_slices + 1, t = ts + 1;
-    const int tx = (int)sbd_compact8((unsigned)tile), ty = (int)sbd_compact8((unsigned)tile >> 1);
+    const int tx = (int)compact8((unsigned)tile), ty = (int)compact8((unsigned)tile >> 1);
     const long img = (long)b * a.n_slices + ts;
-    const float* Tm = a.trans + b * 12;
+    // image coordinates of sorted slot qs: the pre-pass's (launch_sample_bwd), one 8-byte load
     auto project_slot = [&](long qs, float& gx, float& gy) {
-        if (a.gxy) {
-            const s3d_float2 g2 = *reinterpret_cast<const s3d_float2*>(a.gxy + 2 * ((long)b * a.n_qry + qs));
-            gx = g2[0]; gy = g2[1];
-            return;
-        }
-        const long q = a.perm[(long)b * a.n_qry + qs];
-        const float* p = a.qry + ((long)b * a.n_qry + q) * 3;
-        float x = p[0], y = p[1], z = p[2];
-        if (a.flip_yz) {
-            y = -y; z = -z;
-        } else if (a.rot) {
-            const float* R = a.rot + b * 9;
-            const float rx = x * R[0] + y * R[3] + z * R[6];
-            const float ry = x * R[1] + y * R[4] + z * R[7];
-            const float rz = x * R[2] + y * R[5] + z * R[8];
-            x = rx; y = ry; z = rz;
-        }
-        const float X = x * Tm[0] + y * Tm[3] + z * Tm[6] + Tm[9];
-        const float Y = x * Tm[1] + y * Tm[4] + z * Tm[7] + Tm[10];
-        const float Z = x * Tm[2] + y * Tm[5] + z * Tm[8] + Tm[11];
-        gx = fminf(fmaxf(2.f * (X / Z - 0.5f), -1.f), 1.f);
-        gy = fminf(fmaxf(2.f * (Y / Z - 0.5f), -1.f), 1.f);
+        const s3d_float2 g2 = *reinterpret_cast<const s3d_float2*>(a.gxy + 2 * ((long)b * a.n_qry + qs));
+        gx = g2[0]; gy = g2[1];
     };
     auto row_of = [&](long qs) { return ((((long)b * a.groups_per_batch + (qs >> 4)) * T + t) * S3D_GROUP + (qs & 15)) * 128; };
     // the chunk's 64 rows x 128 floats go straight to LDS (global_load_lds, 16 bytes per lane): 32 pieces of two rows, four per wave;
@@ -255,7 +223,7 @@ __global__ __launch_bounds__(SBD_THREADS) void sample_bwd_dense_kernel(const Sam
             const int l = threadIdx.x / SBD_CHUNK, qq = threadIdx.x % SBD_CHUNK;
             const long qs = c0 + qq;
             const int W = G.W[l], C = l < 3 ? 128 : (l == 3 ? 64 : 32);
-            const int ox = 16 * tx * (W - 1) / 255, oy = 16 * ty * (W - 1) / 255;
+            const int ox = tile_origin(tx, W), oy = tile_origin(ty, W);
             int mask = 0;
             // the query's table row, zeroed; its taps are written over it below
             float* tab = l < 3 ? s_fw + qq * SBD_FROW + (l == 0 ? 0 : l == 1 ? 16 : 32) : s_rw + qq * SBD_RROW + (l == 3 ? 0 : 24);
@@ -264,23 +232,15 @@ __global__ __launch_bounds__(SBD_THREADS) void sample_bwd_dense_kernel(const Sam
                 for (int i = 0; i < n4; ++i) st4(tab + 4 * i, zero4());
             }
             if (qs < qs_hi) {
-                const float gx = gx_n, gy = gy_n;
-                const float ix = ((gx + 1.f) / 2.f) * (float)(W - 1);
-                const float iy = ((gy + 1.f) / 2.f) * (float)(W - 1);
-                const float x0f = floorf(ix), y0f = floorf(iy);
-                const int x0 = (int)x0f, y0 = (int)y0f;
-                const float xe = x0f + 1.f, ye = y0f + 1.f;
-                float wx[2] = {xe - ix, ix - x0f}, wy[2] = {ye - iy, iy - y0f};
-                if (x0 < 0 || x0 >= W) wx[0] = 0.f;
-                if (x0 + 1 < 0 || x0 + 1 >= W) wx[1] = 0.f;
-                if (y0 < 0 || y0 >= W) wy[0] = 0.f;
-                if (y0 + 1 < 0 || y0 + 1 >= W) wy[1] = 0.f;
+                const Foot f = make_foot(gx_n, gy_n, W, W);   // factors of columns / rows outside the map are 0
+                const int x0 = f.x0, y0 = f.y0;
+                float wx[2] = {f.wx0, f.wx1}, wy[2] = {f.wy0, f.wy1};
                 const int cov = G.cov[l], fwl = G.fw[l];   // row width of the tables / slot image; the tile's footprint (fwl <= cov)
                 const int rx = x0 - ox, ry = y0 - oy;
-                // The sort's bin (floor((gx + 1) * 127.5), possibly one fma) and this level's pixel index (two roundings) are the same
-                // number up to an ulp: a query within 1e-5 pixels of its tile's border can land one pixel outside the footprint with
-                // the weight ~1e-5 on that side.  It is taken AT the border (the side's weight dropped): the generic path below
-                // would cost the workgroup ~1 ms for it.
+                // The sort's bin (sort_bin: one multiply, possibly fused with its add) and this level's pixel index (level_cell: two
+                // roundings) are the same number up to an ulp: a query within 1e-5 pixels of its tile's border can land one pixel
+                // outside the footprint with the weight ~1e-5 on that side.  It is taken AT the border (the side's weight dropped):
+                // the generic path below would cost the workgroup ~1 ms for it.
                 if (rx == -1 && wx[0] < 1e-3f) wx[0] = 0.f;
                 if (rx + 1 == fwl && wx[1] < 1e-3f) wx[1] = 0.f;
                 if (ry == -1 && wy[0] < 1e-3f) wy[0] = 0.f;
@@ -431,7 +391,7 @@ __global__ __launch_bounds__(256) void sbd_reduce_kernel(const SampleBwdArgs a, 
         const int b = (int)(img / a.n_slices);
         const int* ends = a.bin_ends + (long)b * 65536;
         const int cov = G.cov[l], fwl = G.fw[l], den = 16 * (W - 1);
-        // ox(t) = 16 t (W-1) / 255 is non-decreasing in t: candidates are the t with ox(t) in (x - fw, x]
+        // tile_origin(t, W) is non-decreasing in t: candidates are the t whose origin lies in (x - fw, x]
         const int tx_lo = x - fwl >= 0 ? (x - fwl) * 255 / den : 0, tx_hi = min(15, (x + 1) * 255 / den);
         const int ty_lo = y - fwl >= 0 ? (y - fwl) * 255 / den : 0, ty_hi = min(15, (y + 1) * 255 / den);
         float* o = (l < 3 ? a.dproj[l] : a.dfine[l - 3]) + (long)p * C + 4 * c4;
@@ -439,12 +399,12 @@ __global__ __launch_bounds__(256) void sbd_reduce_kernel(const SampleBwdArgs a, 
         f32x4 s = zero4();
         bool any = false;
         for (int ty = ty_lo; ty <= ty_hi; ++ty) {
-            const int ly = y - 16 * ty * (W - 1) / 255;
+            const int ly = y - tile_origin(ty, W);
             if (ly < 0 || ly >= fwl) continue;
             for (int tx = tx_lo; tx <= tx_hi; ++tx) {
-                const int lx = x - 16 * tx * (W - 1) / 255;
+                const int lx = x - tile_origin(tx, W);
                 if (lx < 0 || lx >= fwl) continue;
-                const int tile = (int)(sbd_spread8((unsigned)tx) | (sbd_spread8((unsigned)ty) << 1));
+                const int tile = (int)morton8((unsigned)tx, (unsigned)ty);
                 const int lo = tile ? ends[256 * tile - 1] : 0, hi = ends[256 * tile + 255];
                 if (lo >= hi) continue;
                 s += ld4(a.partial + ((long)img * 256 + tile) * (long)G.ptotal + G.poff[l] + (ly * cov + lx) * C + 4 * c4);
@@ -461,7 +421,7 @@ static bool sbd_geom(int S, SbdGeom& G) {
     for (int l = 0; l < 5; ++l) {
         const int W = S >> (4 - l);
         G.W[l] = W;
-        G.fw[l] = (16 * (W - 1) + 254) / 255 + 2;
+        G.fw[l] = tile_footprint(W);
         if (l < 3) {
             G.cov[l] = G.fw[l];
             fits = fits && G.fw[l] * G.fw[l] <= 16 * sbd_nmt(l);
@@ -470,8 +430,8 @@ static bool sbd_geom(int S, SbdGeom& G) {
             G.cov[l] = 4 * (l == 3 ? SBD_NB3 : SBD_NB4);
             fits = fits && nb <= (l == 3 ? SBD_NB3 : SBD_NB4);
         }
-        // the tile's bins are level-4 pixels of a 256-wide image ((gx + 1) * 127.5, launch_query_sort); a coarser level's footprint
-        // starts at 16 tx (W-1) / 255: when that is never an integer for tx = 1..15 — or the level IS the 256-wide one, whose
+        // the tile's bins are level-4 pixels of a 256-wide image (sort_bin, query_geom.h); a coarser level's footprint starts at
+        // tile_origin's quotient: when that is never an integer for tx = 1..15 — or the level IS the 256-wide one, whose
         // coordinate is the bin's own expression — a rounding error of the coordinate (~1e-5 pixels) cannot move a tap across it
         if (W < 2) fits = false;
         for (int t = 1; t <= 15 && W != 256; ++t) fits = fits && (16 * t * (W - 1)) % 255 != 0;
@@ -489,35 +449,33 @@ size_t sample_bwd_partial_floats(int S, long batch, int n_slices) {
     return (size_t)batch * n_slices * 256 * G.ptotal;
 }
 
-bool sample_bwd_dense_covers(const SampleBwdArgs& a) {
-    SbdGeom G;
-    if (a.gt || !a.perm || !a.bin_ends || !a.partial || !sbd_geom(a.size, G)) return false;
+// does the dense kernel take this call?  (G: its geometry, when it does)
+static bool sbd_covers(const SampleBwdArgs& a, SbdGeom& G) {
+    if (a.gt || !a.perm || !a.partial || !sbd_geom(a.size, G)) return false;
     if (const char* e = getenv("S3D_SBD_OFF")) if (atoi(e)) return false;   // A/B switch of tools/dbg_sbd.py
     const long n_img = a.groups / a.groups_per_batch * a.n_slices;
     if (n_img * a.size * a.size * 8 >= (1L << 32)) return false;   // sbd_reduce_kernel's 32-bit pixel index (level 4: 8 quads per pixel)
     return true;
 }
 
-// 1 = launched, 0 = this size is not covered (the caller falls back to the atomic kernels), < 0: error.  a.gxy, when given, has
-// been filled by the caller (launch_sample_bwd's pre-pass).
-int launch_sample_bwd_dense(const SampleBwdArgs& a, hipStream_t stream) {
+int launch_sample_bwd_dense(const SampleBwdArgs& a, hipStream_t stream, bool* launched) {
     SbdGeom G;
-    if (!sample_bwd_dense_covers(a) || !sbd_geom(a.size, G)) return 0;
+    *launched = sbd_covers(a, G);
+    if (!*launched) return 0;
     if (const char* e = getenv("S3D_SBD_SLOW_MOD")) G.slow_mod = atoi(e);
     const size_t lds = (size_t)SBD_LDS_FLOATS * sizeof(float);
     static std::atomic<unsigned long long> attr_done{0};
-    if (s3d_set_max_lds(attr_done, {(const void*)sample_bwd_dense_kernel<false>, (const void*)sample_bwd_dense_kernel<true>}, 160 * 1024))
-        return -1;
+    TRY_RET(s3d_set_max_lds(attr_done, {(const void*)sample_bwd_dense_kernel<false>, (const void*)sample_bwd_dense_kernel<true>}, 160 * 1024));
     const long batch = a.groups / a.groups_per_batch;
     if (a.ws34_t16)
         hipLaunchKernelGGL((sample_bwd_dense_kernel<true>), dim3((unsigned)(batch * a.n_slices * 256)), dim3(SBD_THREADS), lds, stream, a, G);
     else
         hipLaunchKernelGGL((sample_bwd_dense_kernel<false>), dim3((unsigned)(batch * a.n_slices * 256)), dim3(SBD_THREADS), lds, stream, a, G);
-    if (hipGetLastError() != hipSuccess) return -1;
+    S3D_LAUNCH_CHECK();
     long quads = 0;
-    for (int l = 0; l < 5; ++l) quads += batch * a.n_slices * G.W[l] * G.W[l] * (sbd_C(l) / 4);   // (each level's count < 2^32: checked in sample_bwd_dense_covers)
+    for (int l = 0; l < 5; ++l) quads += batch * a.n_slices * G.W[l] * G.W[l] * (sbd_C(l) / 4);   // (each level's count < 2^32: checked in sbd_covers)
     const long blocks = (quads + 255) / 256 < 16384 ? (quads + 255) / 256 : 16384;
     hipLaunchKernelGGL(sbd_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a, G, (int)batch);
-    if (hipGetLastError() != hipSuccess) return -1;
-    return 1;
+    S3D_LAUNCH_CHECK();
+    return 0;
 }

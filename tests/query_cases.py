@@ -1,7 +1,8 @@
 """Inputs, float64 references and gates for the conformance of the query front end: rotation / flip, project_coord, the image-
-space locality sort, the bilinear samplers and the token builder (decode.hip: project, make_taps, make_foot, qsort_*,
-project_coord_kernel, sample_planes_kernel, sample_pyramid_kernel, sample_tokens_kernel, sample_tokens_gt_kernel,
-gt_point_tokens_kernel; their backward counterparts in train2.hip / train_sbd.hip).  Nothing here touches a GPU:
+space locality sort, the bilinear samplers and the token builder (query_geom.h: query_xyz, rotate_query, project, level_cell,
+make_taps, make_foot, sort_bin, morton8, tile_origin, tile_footprint; decode.hip: qsort_*, project_coord_kernel,
+sample_planes_kernel, sample_pyramid_kernel, sample_tokens_kernel, sample_tokens_gt_kernel, gt_point_tokens_kernel; the
+backward kernels of train2.hip / train_sbd.hip, which call the same header).  Nothing here touches a GPU:
 tests/test_query_cases.py checks this file on the CPU and tests/test_gpu_query_front_end.py runs it through the entry points.
 
 What slice3d_amd/synth.make_feed_dict cannot give: every object of a batch has its OWN rotation and camera matrix (CAMERAS,
