@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define S3D_VERSION 124         /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding; 119: s3d_mesh_render_*; 120: s3d_unet_encode_fwd computes the decoder's slice-invariant terms once per image, the weights-only ones in s3d_unet_pack (other packed-image and workspace sizes: query them); 121: up2-up4 run ConvTranspose and the first 3x3's up half as one convolution of the low-resolution map with weights composed in s3d_unet_pack (packed-image and workspace sizes change again); 122: s3d_mesh_simplify_*; 123: s3d_conv_plan_describe; 124: s3d_mesh_topology_* */
+#define S3D_VERSION 125         /* 0.1.1: s3d_conv_fwd prec semantics, s3d_conv_gn_supported; 111: s3d_decode_set_last_fused, s3d_decode_set_shared_footprint; 112: S3D_PREC_F16 accepted by s3d_train_*; 113: atomic-free sampling backward (bit-reproducible s3d_train_* gradients, larger workspace); 114: s3d_qkv_attention_ws_* serve head width 48; 115: s3d_add_nchw_fwd; 116: s3d_conv_strided_fwd, s3d_wide_attention_fwd, s3d_image_normalize_fwd; 117: mesh evaluation (s3d_mesh_contains_*, s3d_nn_sqdist, s3d_surface_sample); 118: s3d_mesh_dist_*, s3d_mesh_winding; 119: s3d_mesh_render_*; 120: s3d_unet_encode_fwd computes the decoder's slice-invariant terms once per image, the weights-only ones in s3d_unet_pack (other packed-image and workspace sizes: query them); 121: up2-up4 run ConvTranspose and the first 3x3's up half as one convolution of the low-resolution map with weights composed in s3d_unet_pack (packed-image and workspace sizes change again); 122: s3d_mesh_simplify_*; 123: s3d_conv_plan_describe; 124: s3d_mesh_topology_*; 125: s3d_decode_points_stages_fwd also captures the token tensor after layers 0 and 1 (s3d_decode_stages_floats grows) */
 #define S3D_E_ARG (-1)           /* bad argument / unsupported shape */
 #define S3D_E_WORKSPACE (-2)     /* workspace or packed-weight buffer too small */
 #define S3D_E_ROUNDS (-3)        /* s3d_mesh_topology_run: the component labels did not converge within its round bound */
@@ -188,7 +188,8 @@ int s3d_decode_points_fwd(const void* head_packed, const S3dLatent* latent, cons
  * (fc_p / fc_s output models.py:79-82, token 0 after each layer of att_decoder models.py:83): stages holds
  * s3d_decode_stages_floats() floats = the token tensor [G][n_slices+1][16][128] (G = B*ceil(Q/16); row of query q of
  * object b: group b*ceil(Q/16) + q/16, lane q%16; token 0 = fc_p, token 1+s = fc_s of slice s), then [3][G*16][128] token-0
- * rows after layers 0, 1, 2.  One pass in caller order: Q < 4096 per object. */
+ * rows after layers 0, 1, 2, then [2][G][n_slices+1][16][128]: the whole token tensor after layer 0 and after layer 1 (every
+ * token row the two full layers write, in the layout of the first block).  One pass in caller order: Q < 4096 per object. */
 size_t s3d_decode_stages_floats(int batch, long n_qry, int n_slices);
 int s3d_decode_points_stages_fwd(const void* head_packed, const S3dLatent* latent, const float* qry, const float* rot,
                                  const float* trans, int flip_yz, float* sdf_out, float* stages, int batch, long n_qry,

@@ -1109,7 +1109,8 @@ static int decode_layers(const DecodeStack& D, hipStream_t s, long gs, long gn, 
     float* Xs = D.X + (size_t)gs * T * S3D_GROUP * 128;
     float* X0s = D.X0 + (size_t)gs * S3D_GROUP * 128;
     float* lasts = D.last + (size_t)gs * S3D_GROUP * S3D_LAST_ROW_FLOATS;
-    const size_t rows0 = (size_t)gn * S3D_GROUP * 128;   // with stages: token 0 after layer l at stages + (T + l) * rows0
+    const size_t rows0 = (size_t)gn * S3D_GROUP * 128;   // with stages: token 0 after layer l at stages + (T + l) * rows0,
+                                                         // X after layer l < 2 at stages + (T + 3 + l * T) * rows0
     for (int l = 0; l < S3D_N_LAYERS; ++l) {
         const LayerPtrs lp = layer_ptrs(D.b, D.H, l);
         const bool last = l == S3D_N_LAYERS - 1;
@@ -1134,7 +1135,15 @@ static int decode_layers(const DecodeStack& D, hipStream_t s, long gs, long gn, 
                 TRY(launch_ffn_layer(Xs + (size_t)f0 * T * S3D_GROUP * 128, fc * T * S3D_GROUP, lp, nullptr, nullptr, nullptr,
                                      1.f, D.gpb, D.n_qry, D.g0 + gs + f0, ffn_prec, nullptr, s));
             }
-            if (d) TRY(launch_tok0_copy(Xs, d, gn, T, 0, 128, s));
+            if (d) {
+                TRY(launch_tok0_copy(Xs, d, gn, T, 0, 128, s));
+                // and every token row of the layer's output X: [2][gn][T][16][128] behind the three token-0 blocks
+                if (hipMemcpyAsync(D.stages + (size_t)(T + S3D_N_LAYERS + l * T) * rows0, Xs, (size_t)T * rows0 * sizeof(float),
+                                   hipMemcpyDeviceToDevice, s) != hipSuccess) {
+                    s3d_set_error("decode stages: memcpy failed");
+                    return (int)hipErrorUnknown;
+                }
+            }
         } else {
             ProfScope prof_(S3D_PROF_FFN_FINAL, s);
             if (d) {   // the final kernel keeps the layer's output rows in registers (LayerNorm -> fc_out): the capture
@@ -1258,11 +1267,12 @@ extern "C" int s3d_decode_points_fwd(const void* head_packed, const S3dLatent* l
 
 // s3d_decode_points_fwd that also hands out the intermediate rows the reference's stage goldens probe (models.py:79-83):
 // stages = [G][T][16][128] token tensor after fc_p / fc_s (token 0 = fc_p(qry_rot), token 1 + s = fc_s of slice s; row of
-// query q of object b: group b * ceil(Q/16) + q / 16, lane q % 16), then [3][G*16][128]: token 0 after each encoder layer.
+// query q of object b: group b * ceil(Q/16) + q / 16, lane q % 16), then [3][G*16][128]: token 0 after each encoder layer,
+// then [2][G][T][16][128]: the whole token tensor X after layer 0 and after layer 1 (the layout of the first block).
 // Debug / test entry point: one decode pass, queries in caller order (Q < 4096 per object).
 extern "C" size_t s3d_decode_stages_floats(int batch, long n_qry, int n_slices) {
     const size_t G = (size_t)((n_qry + S3D_GROUP - 1) / S3D_GROUP) * batch;
-    return G * S3D_GROUP * 128 * (size_t)(n_slices + 1 + S3D_N_LAYERS);
+    return G * S3D_GROUP * 128 * (size_t)(3 * (n_slices + 1) + S3D_N_LAYERS);
 }
 extern "C" int s3d_decode_points_stages_fwd(const void* head_packed, const S3dLatent* latent, const float* qry,
                                             const float* rot, const float* trans, int flip_yz, float* sdf_out,

@@ -534,7 +534,8 @@ class Slices3DRegModel(HipModel, nn.Module):
         """Debug / test form of decode_sdf that also returns the rows the reference's stage probes look at: a dict with
         'sdf' (B,Q), 'fc_p' (B,Q,128) = fc_p(qry_rot), 'fc_s' (B,Q,n_slices,128) = fc_s of the sampled pyramid
         (models.py:79-82) and 'layer0' / 'layer1' / 'layer2' (B,Q,128) = token 0 after each layer of att_decoder
-        (models.py:83).  One decode pass in caller order: Q < 4096 per object."""
+        (models.py:83), and 'x0' / 'x1' (B,Q,n_slices+1,128) = every token row after layers 0 and 1.  One decode pass in
+        caller order: Q < 4096 per object."""
         lib = self._require_lib()
         self._require_eval()
         mode = self.mode if mode is None else mode
@@ -549,7 +550,7 @@ class Slices3DRegModel(HipModel, nn.Module):
         g = gpb * b
         out = torch.empty((b, q), dtype=torch.float32, device=qry.device)
         n_st = lib.s3d_decode_stages_floats(b, q, ns)
-        assert n_st == g * 16 * 128 * (t + 3)
+        assert n_st == g * 16 * 128 * (3 * t + 3)
         st = torch.empty(n_st, dtype=torch.float32, device=qry.device)
         ws = self._workspace("decode", lib.s3d_decode_workspace_bytes(b, q, ns))
         _lib.check(lib.s3d_decode_points_stages_fwd(self._head_packed.data_ptr(), C.byref(c._latent_struct), qry.data_ptr(),
@@ -557,11 +558,15 @@ class Slices3DRegModel(HipModel, nn.Module):
                                                     1 if mode == "test" else 0, out.data_ptr(), st.data_ptr(), b, q, ns,
                                                     self.prec, ws.data_ptr(), ws.numel(), self._stream()),
                    "s3d_decode_points_stages_fwd")
-        tok = st[:g * t * 16 * 128].view(b, gpb, t, 16, 128).permute(0, 1, 3, 2, 4).reshape(b, gpb * 16, t, 128)[:, :q]
+        n_tok, n_row = g * t * 16 * 128, g * 16 * 128
+        rows = lambda x: x.view(b, gpb, t, 16, 128).permute(0, 1, 3, 2, 4).reshape(b, gpb * 16, t, 128)[:, :q]
+        tok = rows(st[:n_tok])
         res = {"sdf": out, "fc_p": tok[:, :, 0], "fc_s": tok[:, :, 1:]}
-        lay = st[g * t * 16 * 128:].view(3, b, gpb * 16, 128)[:, :, :q]
+        lay = st[n_tok:n_tok + 3 * n_row].view(3, b, gpb * 16, 128)[:, :, :q]
         for i in range(3):
             res["layer%d" % i] = lay[i]
+        for i in range(2):
+            res["x%d" % i] = rows(st[n_tok + 3 * n_row + i * n_tok:n_tok + 3 * n_row + (i + 1) * n_tok])
         return res
 
     def decode(self, p, c, **kwargs):
